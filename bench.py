@@ -9,17 +9,20 @@ step    : embed -> 24 blocks -> head -> masked-token CE (+top-1/5) -> full backw
           (reduce-scatter / sharded AdamW / all-gather when N>1) -> AdamW.  Inputs are resident in HBM
           before timing starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--secondary none|light|full|c4|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--windows 3] [--secondary none|light|full|c4|c5] [--no-cpu-baseline] ...
   (--secondary c4 / c5: ONLY that configuration's legs, no headline step — the process a rocprofv3 profile of config 4 / 5 wraps)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` = the GEMM kernel family (93 % of the step's FLOPs),
-achieved = algorithmic FLOPs / HIP-event time on the launch stream, measured live after the timed
-region; `cpu_baseline` = the CPU oracle (kind "port") timed on this box's host cores on a bounded
-sample of the same workload; `secondary` (N = 1 only, outside the timed region) = the other metrics
-of SURVEY.md §8(d): the step with the separate optimizer (what every data-parallel rank runs), the eval
-forward, the t sweep, a variable-t run, the samplers at C2, the C4 revise schedule and the HBM rate of
-the embedding gather / scatter kernels.
+Rank 0 prints ONE JSON line.  A plain run sets up, runs one untimed step (GEMM tuner), the warm-up, ONE window of
+exactly --steps timed steps, and prints the headline (`value`, `ms_per_step`); --dump-outputs DIR writes what the
+last timed step computed (dump_outputs).  Everything else is measured only with --full, outside the timed window:
+more windows (spread, GPU clocks), `host_enqueue_ms_per_step`, `roofline` = the GEMM kernel family (93 % of the
+step's FLOPs), achieved = algorithmic FLOPs / HIP-event time on the launch stream; the data-parallel
+self-description; `cpu_baseline` = the CPU oracle (kind "port") timed on this box's host cores on a bounded
+sample of the same workload; `secondary` (N = 1 only) = the other metrics of SURVEY.md §8(d): the step with the
+separate optimizer (what every data-parallel rank runs), the eval forward, the t sweep, a variable-t run, the
+samplers at C2, the C4 revise schedule and the HBM rate of the embedding gather / scatter kernels.
 """
 import argparse
 import ctypes as C
@@ -46,6 +49,24 @@ def synthetic_batch(B, shape, rank, device):
     x = torch.randint(0, 16384, (B, *shape), generator=g)
     idx = torch.stack([torch.randperm(N, generator=g) for _ in range(B)])
     return x.to(device), idx.to(device)
+
+
+DUMP_SAMPLES = {"W": 4 << 20, "P": 1 << 20}      # fp32 elements of the updated weights written by --dump-outputs (20 MB)
+
+
+def dump_outputs(out_dir, stats, native):
+    """What the timed step hands its caller, after the last timed step: the statistics row TrainLoop.step returns
+    ([CE sum, #top-1, #top-5, #rows, loss], float64) and the fp32 master weights it updated in place — the Linear
+    weights W and the other parameters P, each whole if small, else a fixed sample (seeded positions, the same in every
+    run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "step_stats.npy"), stats.detach().double().cpu().numpy())
+    g = torch.Generator().manual_seed(20240601)
+    for name, flat in (("W", native.W), ("P", native.P)):
+        n, k = flat.numel(), DUMP_SAMPLES[name]
+        pos = torch.arange(n) if n <= k else torch.randint(0, n, (k,), generator=g).sort().values
+        np.save(os.path.join(out_dir, f"master_{name}_sample.npy"), flat[pos.to(flat.device)].float().cpu().numpy())
 
 
 def cpu_model_name():
@@ -527,13 +548,25 @@ def main():
     ap.add_argument("--batch", type=int, default=6)
     ap.add_argument("--t", type=float, default=0.5)
     ap.add_argument("--dropout", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps: the first is the judged one, the others report the spread")
-    ap.add_argument("--secondary", default="full", choices=["none", "light", "full", "c4", "c5"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--windows", type=int, default=None, help="--full: timed windows of --steps steps (default 3): the first is the judged one, the others report the spread")
+    ap.add_argument("--secondary", default=None, choices=["none", "light", "full", "c4", "c5"], help="--full: which secondary legs run (default full)")
     ap.add_argument("--preset", default="sky_16f", choices=["sky_16f", "tiny"])
     ap.add_argument("--c5-batch", type=int, default=16, help="videos per batch of the config-5 leg (the shipped Taichi script: 16)")
     ap.add_argument("--c4-legs", default="revise,sample,bootstrap,train", help="which config-4 legs run (profiling one at a time)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.secondary not in (None, "none") or (args.windows or 1) > 1):
+        ap.error("--secondary and more than one window measure beyond the headline: add --full")
+    if args.dump_outputs and args.secondary in ("c4", "c5"):
+        ap.error("--dump-outputs needs the headline step, which --secondary c4 / c5 does not run")
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
+    if args.secondary is None:
+        args.secondary = "full" if args.full else "none"
 
     # `python bench.py --gpus N` without a torch.distributed environment: start the N ranks as a child process (before anything
     # here touches the GPU), relay rank 0's line, exit with the child's return code (mebt_amd/launch.py)
@@ -629,7 +662,7 @@ def main():
         reducer.sync_tune_table()      # every rank, i.e. a drained GPU queue) happens inside the timed region
         loop.hold_tune_sync = True
     sync()
-    gpu_before = gpu_state(local_rank) if rank == 0 else None
+    gpu_before = gpu_state(local_rank) if args.full and rank == 0 else None
     wire0 = reducer.bytes_on_wire
 
     def window():
@@ -647,12 +680,45 @@ def main():
             el = float(tt.item())
         return el, st_
 
-    sampler = ClockSampler(local_rank) if rank == 0 else None
+    sampler = ClockSampler(local_rank) if args.full and rank == 0 else None
     if sampler is not None:
         sampler.__enter__()
     elapsed, stats = window()            # THE timed region: `value` / `ms_per_step` come from this window alone
     wire1 = reducer.bytes_on_wire
-    # ... and more windows of the same length behind it (outside the judged region): their spread says how much of a difference
+    if args.dump_outputs:                # before any further step changes the weights
+        loop.consolidate(optimizer_state=False)      # sharded data parallel: complete fp32 masters on every rank (a collective)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, stats, loop.native)
+        sync()
+    stats = stats.cpu()
+    n_targets = int(stats[3])                                  # masked tokens scored per rank per step
+    ms = 1e3 * elapsed / args.steps
+    value = world * n_targets * args.steps / elapsed
+    wire_bytes_per_step = (wire1 - wire0) / max(1, args.steps)     # payload of the timed steps only
+    out = {"metric": "masked video tokens/sec/GPU (train step, 24L d=1024, 1024+256 tok)",
+           "value": round(value, 1), "unit": "masked tokens/s (whole job)", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+           "per_gpu": round(value / world, 1),
+           "config": {"workload": "Sky-Timelapse 16f MeBT train step: 24L/1024d/16h, 1024 VQ tokens + 256 latents, "
+                                  f"batch {args.batch}/GPU, t={args.t} (NC=NT={n_targets // args.batch}), "
+                                  "fwd + masked CE + bwd + AdamW" + ((f" + {'all-to-all (fp32 sum at the owner)' if (reducer.wire == 'bf16' and reducer.exchange == 'a2a') else 'reduce-scatter'} / sharded AdamW / all-gather ({reducer.wire} wire)" if reducer.mode == "sharded" else " + bucketed fp32 all-reduce") if reducer.active else ""),
+                      "global_batch": args.batch * world, "parallelism": f"dp{world}", "dropout": args.dropout,
+                      "optimizer": "in-backward (fused into the weight-gradient launches)" if loop.fused_optimizer else
+                                   ("sharded over ranks" if reducer.active and reducer.mode == "sharded" else
+                                    "replicated, behind a bucketed fp32 all-reduce" if reducer.active else "separate"),
+                      "loss": round(float(stats[4]), 4)}}
+    if not args.full:
+        out["data_parallel"] = {"dp_mode": reducer.mode, "wire": reducer.wire if reducer.mode == "sharded" else "fp32", "backend": backend,
+                                "dp_fallback": dp_fallback, "bytes_on_wire_per_step": int(wire_bytes_per_step)} if reducer.active else None
+        if rank == 0:
+            os.write(real_stdout, (json.dumps(out) + "\n").encode())
+        if world > 1 or dp_force:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full: more windows of the same length behind it (outside the judged region): their spread says how much of a difference
     # between two runs of this line is the box and how much the code
     # the extra windows also carry a one-wave clock probe on a second stream (mebt_debug_clock_probe: shader-clock ticks per 100 MHz
     # reference tick over ~70 % of the window): the clock the chip really runs this step at - the judged window stays untouched
@@ -683,10 +749,6 @@ def main():
         sampler.__exit__()
     gpu_after = gpu_state(local_rank) if rank == 0 else None
     win_ms = [round(1e3 * e / args.steps, 3) for e in [elapsed] + extra]
-    stats = stats.cpu()
-    n_targets = int(stats[3])                                  # masked tokens scored per rank per step
-    ms = 1e3 * elapsed / args.steps
-    wire_bytes_per_step = (wire1 - wire0) / max(1, args.steps)     # payload of the timed steps only
     # host side of a step: wall time of two step() calls that only enqueue (empty queue in front, no synchronisation inside)
     sync()
     h0 = time.perf_counter()
@@ -694,7 +756,6 @@ def main():
         loop.step(x, idx, t=args.t)
     host_enqueue_ms = 1e3 * (time.perf_counter() - h0) / 2
     sync()
-    value = world * n_targets * args.steps / elapsed
 
     # dominant kernel family: MFMA GEMMs — time every launch of 2 more steps with HIP events on the
     # launch stream (rank 0 records; every rank runs the steps because they contain collectives).  Taken BEFORE the
@@ -804,10 +865,10 @@ def main():
                 nb -= nb % (4 * world)
                 send = torch.zeros(nb, dtype=torch.bfloat16, device=device)
                 recv = torch.empty(nb, dtype=torch.bfloat16, device=device)
-                out = torch.empty(nb // world, dtype=torch.bfloat16, device=device)
+                shard = torch.empty(nb // world, dtype=torch.bfloat16, device=device)
                 exchange_probe = {}
                 for name, fn in (("all_to_all_ms", lambda: dist.all_to_all_single(recv, send)),
-                                 ("reduce_scatter_ms", lambda: dist.reduce_scatter_tensor(out, send, op=dist.ReduceOp.SUM))):
+                                 ("reduce_scatter_ms", lambda: dist.reduce_scatter_tensor(shard, send, op=dist.ReduceOp.SUM))):
                     ts_ = []
                     for it in range(7):
                         sync()
@@ -823,7 +884,7 @@ def main():
                             ts_.append(1e3 * el)
                     exchange_probe[name] = round(sorted(ts_)[len(ts_) // 2], 3)
                 exchange_probe["bucket_MB"] = round(nb * 2 / 1e6, 1)
-                del send, recv, out
+                del send, recv, shard
             except Exception as e:          # noqa: BLE001
                 exchange_probe = {"error": f"{type(e).__name__}: {e}"}
         dp = {"dp_mode": reducer.mode, "wire": reducer.wire if reducer.mode == "sharded" else "fp32",
@@ -850,29 +911,16 @@ def main():
               "comm_env": comm_env()}
 
     if rank == 0:
-        out = {"metric": "masked video tokens/sec/GPU (train step, 24L d=1024, 1024+256 tok)",
-               "value": round(value, 1), "unit": "masked tokens/s (whole job)", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak",
-               "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-               "per_gpu": round(value / world, 1),
-               "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
-               "windows": {"ms_per_step": win_ms, "median": sorted(win_ms)[len(win_ms) // 2], "min": min(win_ms), "max": max(win_ms),
-                           "note": f"{len(win_ms)} back-to-back windows of {args.steps} steps, each barrier + synchronize bracketed; `value` is the FIRST"},
-               "gpu_state": {"before": gpu_before, "after": gpu_after, "during_windows": sampler.summary() if sampler is not None else None,
-                             "shader_clock_ghz_in_extra_windows": clock_ghz,
-                             "note": "amdgpu sysfs: current sclk / mclk / fclk level, power cap / average before and after the windows (idle readings), "
-                                     "and sclk / power sampled every 25 ms by a host thread while they run (on this pool the sysfs sclk does not follow the load: "
-                                     "`shader_clock_ghz_in_extra_windows` is measured in a kernel, s_memtime against the 100 MHz s_memrealtime, beside the steps of the "
-                                     "windows behind the judged one)"},
-               "config": {"workload": "Sky-Timelapse 16f MeBT train step: 24L/1024d/16h, 1024 VQ tokens + 256 latents, "
-                                      f"batch {args.batch}/GPU, t={args.t} (NC=NT={n_targets // args.batch}), "
-                                      "fwd + masked CE + bwd + AdamW" + ((f" + {'all-to-all (fp32 sum at the owner)' if (reducer.wire == 'bf16' and reducer.exchange == 'a2a') else 'reduce-scatter'} / sharded AdamW / all-gather ({reducer.wire} wire)" if reducer.mode == "sharded" else " + bucketed fp32 all-reduce") if reducer.active else ""),
-                          "global_batch": args.batch * world, "parallelism": f"dp{world}", "dropout": args.dropout,
-                          "optimizer": "in-backward (fused into the weight-gradient launches)" if loop.fused_optimizer else
-                                       ("sharded over ranks" if reducer.active and reducer.mode == "sharded" else
-                                        "replicated, behind a bucketed fp32 all-reduce" if reducer.active else "separate"),
-                          "loss": round(float(stats[4]), 4)},
-               "roofline": roof, "data_parallel": dp}
+        out.update({"host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
+                    "windows": {"ms_per_step": win_ms, "median": sorted(win_ms)[len(win_ms) // 2], "min": min(win_ms), "max": max(win_ms),
+                                "note": f"{len(win_ms)} back-to-back windows of {args.steps} steps, each barrier + synchronize bracketed; `value` is the FIRST"},
+                    "gpu_state": {"before": gpu_before, "after": gpu_after, "during_windows": sampler.summary() if sampler is not None else None,
+                                  "shader_clock_ghz_in_extra_windows": clock_ghz,
+                                  "note": "amdgpu sysfs: current sclk / mclk / fclk level, power cap / average before and after the windows (idle readings), "
+                                          "and sclk / power sampled every 25 ms by a host thread while they run (the sysfs sclk need not follow the load: "
+                                          "`shader_clock_ghz_in_extra_windows` is measured in a kernel, s_memtime against the 100 MHz s_memrealtime, beside the steps of the "
+                                          "windows behind the judged one)"},
+                    "roofline": roof, "data_parallel": dp})
         # the legs below run outside the timed region; a failure in one of them must not cost the headline line
         if world == 1 and args.secondary != "none" and args.preset == "sky_16f":
             try:

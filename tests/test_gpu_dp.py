@@ -36,11 +36,11 @@ def _batches(n=4):
     return xs, idxs, (0.45, 0.3, 0.0)            # t = 0: NC = 0 (empty key/value reductions: zero-filled gradient slices)
 
 
-def _worker(rank, world, port, dtype, mode, wire, defer, ret, overlap=True, check_buckets=True, total=4):
+def _worker(rank, world, port, dtype, mode, wire, defer, ret, overlap=True, check_buckets=True, total=4, device=0):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ["MEBT_DP_DEFER_GATHER"] = "1" if defer else "0"
-    torch.cuda.set_device(0)
+    torch.cuda.set_device(device)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from mebt_amd.parallel import GradReducer
@@ -208,7 +208,12 @@ def test_bf16_wire_against_fp32_wire_at_four_ranks(ranks):
     by all-to-all and summed in fp32 by the owner (the default), (b) reduced in bf16 by reduce-scatter (MEBT_DP_EXCHANGE=rs: N - 1
     roundings of partial sums per element), (c) reduced in fp32.  All runs keep the DDP contract against one process x batch N
     (same bounds as the two-rank test), and the reduced gradients themselves - seen through AdamW's first moments - differ from
-    the fp32 run by measured, gated amounts; (a) must be closer to it than (b)."""
+    the fp32 run by measured, gated amounts; (a) must be closer to it than (b).  Four ranks share GPU 0 (five processes hold it,
+    this one included).  Eight ranks take one GPU each: on one GPU they would be nine processes holding it at once, and GPU
+    machines shared between jobs may cap that count below nine, so with fewer than eight GPUs the case skips."""
+    one_per_gpu = ranks > 4
+    if one_per_gpu and torch.cuda.device_count() < ranks:
+        pytest.skip(f"needs {ranks} GPUs (one rank each), found {torch.cuda.device_count()}")
     import torch.multiprocessing as mp
     from mebt_amd.trainer import TrainLoop
     ctx = mp.get_context("spawn")
@@ -219,7 +224,8 @@ def test_bf16_wire_against_fp32_wire_at_four_ranks(ranks):
         port = free_port()
         os.environ["MEBT_DP_EXCHANGE"] = exchange                 # inherited by the spawned ranks
         try:
-            procs = [ctx.Process(target=_worker, args=(r, ranks, port, "bf16", "sharded", wire, True, ret, True, False, ranks)) for r in range(ranks)]
+            procs = [ctx.Process(target=_worker, args=(r, ranks, port, "bf16", "sharded", wire, True, ret, True, False, ranks, r if one_per_gpu else 0))
+                     for r in range(ranks)]
             for p in procs:
                 p.start()
         finally:
@@ -396,7 +402,7 @@ def test_bench_gpus_2_starts_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["MEBT_BENCH_SHARE_GPU"] = "1"
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--secondary", "none", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--secondary", "none", "--no-cpu-baseline"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -425,7 +431,7 @@ def test_bench_fallback_to_allreduce_runs_under_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update({"MEBT_DP_FORCE": "1", "MEBT_BENCH_FAIL_SHARDED": "1", "MASTER_PORT": str(36100 + os.getpid() % 1500)})
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--secondary", "none", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--full", "--secondary", "none", "--no-cpu-baseline"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -436,3 +442,28 @@ def test_bench_fallback_to_allreduce_runs_under_rccl():
     assert dp["dp_mode"] == "allreduce" and dp["wire"] == "fp32" and dp["backend"] == "nccl" and dp["rccl_ranks"] == 1
     assert r["value"] > 0 and r["config"]["optimizer"].startswith("replicated") and abs(r["config"]["loss"] - 9.7) < 0.5
     assert r["roofline"]["frac"] > 0
+
+
+def test_bench_plain_data_parallel_line_and_dump_under_rccl(tmp_path):
+    """A plain `bench.py` run (no --full) of the data-parallel path - a one-rank RCCL group with the reducer forced active
+    (MEBT_DP_FORCE=1): the line names the path that ran without measuring more, and --dump-outputs gathers the sharded fp32
+    masters (`consolidate`, a collective) before writing them."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MEBT_BENCH_FAIL_SHARDED")}
+    env.update({"MEBT_DP_FORCE": "1", "MASTER_PORT": str(36200 + os.getpid() % 1500)})
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         cwd=root, env=env, capture_output=True, text=True, timeout=1500)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["value"] > 0 and "roofline" not in r
+    assert r["data_parallel"] == {"dp_mode": "sharded", "wire": "bf16", "backend": "nccl", "dp_fallback": None,
+                                  "bytes_on_wire_per_step": r["data_parallel"]["bytes_on_wire_per_step"]}
+    assert r["data_parallel"]["bytes_on_wire_per_step"] > 1e9
+    st = np.load(tmp_path / "step_stats.npy")
+    assert abs(st[4] - r["config"]["loss"]) <= 1e-4
+    for k in ("W", "P"):
+        a = np.load(tmp_path / f"master_{k}_sample.npy")
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()

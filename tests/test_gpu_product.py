@@ -679,3 +679,44 @@ def test_gpt_forward_boundary_backward(dtype):
     with torch.no_grad():
         inf, _ = model.transformer(sos.to(DEV), ctx.to(DEV), tgt.to(DEV), None, 0.)
     assert not inf.requires_grad and (inf.cpu() - ref.detach()).abs().max().item() < tol
+
+
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_ones_outputs(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: ONE line with the headline fields, exactly K timed steps, nothing measured
+    beyond them; `--dump-outputs DIR` writes the last timed step's statistics row and a fixed sample of the fp32 weights it updated
+    (float arrays, 64 MB at most).  Two runs with the same arguments and the same GEMM picks (one tune cache: the first run tunes
+    and writes it, the second reads it) compute the same arrays up to the order of atomically accumulated sums - far closer than
+    the ~lr per element that any change of the inputs, the weights or the sample positions would move the updated weights."""
+    import json, subprocess, sys
+    from mebt_amd import presets
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MEBT_DP_FORCE")}
+    env["MEBT_GEMM_TUNE_CACHE"] = str(tmp_path / "tune_cache.txt")
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, "bench.py", "--preset", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                             cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["higher_is_better"] is True and r["dtype"] == "bf16"
+        assert r["value"] > 0 and r["ms_per_step"] > 0 and r["metric"] and r["unit"]
+        assert not {"roofline", "windows", "gpu_state", "host_enqueue_ms_per_step", "secondary", "cpu_baseline"} & set(r), sorted(r)
+        files = sorted(os.listdir(d))
+        assert files == ["master_P_sample.npy", "master_W_sample.npy", "step_stats.npy"], files
+        assert sum((d / f).stat().st_size for f in files) <= 64 << 20
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        st = arrs["step_stats"]
+        assert st.shape == (5,) and abs(st[4] - r["config"]["loss"]) <= 1e-4 and st[3] > 0 and st[3] % 6 == 0      # batch 6
+        runs.append(arrs)
+    a, b = runs
+    assert (tmp_path / "tune_cache.txt").is_file()
+    np.testing.assert_allclose(b["step_stats"][[0, 4]], a["step_stats"][[0, 4]], rtol=1e-5)      # CE sum, loss
+    assert np.abs(a["step_stats"][1:4] - b["step_stats"][1:4]).max() <= 1                         # top-1 / top-5 hits, rows
+    lr = presets.tiny().exp.exact_lr
+    for k in ("master_W_sample", "master_P_sample"):
+        assert a[k].shape == b[k].shape
+        assert_same_trajectory(a[k], b[k], k, lr=lr)

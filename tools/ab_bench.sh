@@ -5,6 +5,6 @@ A="$1"; B="$2"; R=${3:-3}; S=${4:-30}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
 export MEBT_GEMM_TUNE_CACHE=${MEBT_GEMM_TUNE_CACHE:-/tmp/ab_tune_cache.txt}
-run() { env $1 python3 bench.py --steps $S --warmup 8 --secondary none --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['roofline']['gemm_ms_per_step'])"; }
+run() { env $1 python3 bench.py --steps $S --warmup 8 --full --secondary none --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['roofline']['gemm_ms_per_step'])"; }
 echo "populate: $(run "$A")  $(run "$B")"
 for i in $(seq 1 $R); do echo "A [$A]: $(run "$A")    B [$B]: $(run "$B")"; done

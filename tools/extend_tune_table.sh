@@ -7,12 +7,13 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"; mkdir -p gpurun_out/tune
 export MEBT_GEMM_TUNE_CACHE=$ROOT/gpurun_out/tune/added.txt
 rm -f $MEBT_GEMM_TUNE_CACHE
-python3 bench.py --no-cpu-baseline > gpurun_out/tune/ext_full.json 2> gpurun_out/tune/ext_full.err
-python3 bench.py --secondary c5 --c5-batch 4 --no-cpu-baseline > gpurun_out/tune/ext_c5b4.json 2>> gpurun_out/tune/ext_full.err
-MEBT_SAMPLE_BF16_LOGITS=0 python3 bench.py --secondary c4 --c4-legs revise,sample,bootstrap --no-cpu-baseline > gpurun_out/tune/ext_c4_f32logits.json 2>> gpurun_out/tune/ext_full.err
+OUT=$(dirname "$MEBT_GEMM_TUNE_CACHE")
+python3 bench.py --full --no-cpu-baseline > $OUT/ext_full.json 2> $OUT/ext_full.err
+python3 bench.py --full --secondary c5 --c5-batch 4 --no-cpu-baseline > $OUT/ext_c5b4.json 2>> $OUT/ext_full.err
+MEBT_SAMPLE_BF16_LOGITS=0 python3 bench.py --full --secondary c4 --c4-legs revise,sample,bootstrap --no-cpu-baseline > $OUT/ext_c4_f32logits.json 2>> $OUT/ext_full.err
 # the data-parallel step (weight gradients stored as bf16 / fp32 instead of consumed by the fused AdamW epilogue: other grouped signatures)
-MEBT_DP_FORCE=1 python3 bench.py --secondary none --no-cpu-baseline --steps 5 > gpurun_out/tune/ext_dp.json 2>> gpurun_out/tune/ext_full.err
-MEBT_DP_FORCE=1 MEBT_DP_MODE=allreduce python3 bench.py --secondary none --no-cpu-baseline --steps 5 > gpurun_out/tune/ext_dp_ar.json 2>> gpurun_out/tune/ext_full.err
+MEBT_DP_FORCE=1 python3 bench.py --full --secondary none --no-cpu-baseline --steps 5 > $OUT/ext_dp.json 2>> $OUT/ext_full.err
+MEBT_DP_FORCE=1 MEBT_DP_MODE=allreduce python3 bench.py --full --secondary none --no-cpu-baseline --steps 5 > $OUT/ext_dp_ar.json 2>> $OUT/ext_full.err
 python3 - <<'PY'
 import os
 root = os.environ.get("GRAFT_REPO_ROOT", ".")

@@ -7,9 +7,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"; mkdir -p gpurun_out/tune
 export MEBT_GEMM_TUNE_SHIPPED=0 MEBT_GEMM_TUNE_CACHE=$ROOT/gpurun_out/tune/gfx950.txt
 rm -f $MEBT_GEMM_TUNE_CACHE
-python3 bench.py --no-cpu-baseline > gpurun_out/tune/bench_full.json 2> gpurun_out/tune/bench_full.err
-MEBT_DP_FORCE=1 python3 bench.py --secondary none --no-cpu-baseline --steps 5 > gpurun_out/tune/bench_dp.json 2> gpurun_out/tune/bench_dp.err
-MEBT_DP_FORCE=1 MEBT_DP_MODE=allreduce python3 bench.py --secondary none --no-cpu-baseline --steps 5 > gpurun_out/tune/bench_dp_ar.json 2>> gpurun_out/tune/bench_dp.err
+OUT=$(dirname "$MEBT_GEMM_TUNE_CACHE")
+python3 bench.py --full --no-cpu-baseline > $OUT/bench_full.json 2> $OUT/bench_full.err
+MEBT_DP_FORCE=1 python3 bench.py --full --secondary none --no-cpu-baseline --steps 5 > $OUT/bench_dp.json 2> $OUT/bench_dp.err
+MEBT_DP_FORCE=1 MEBT_DP_MODE=allreduce python3 bench.py --full --secondary none --no-cpu-baseline --steps 5 > $OUT/bench_dp_ar.json 2>> $OUT/bench_dp.err
 # in-step refinement of the benchmarked step's signatures (tools/step_tune.py: a fresh in-process tuning, then the runner-ups of every
 # signature timed inside the step; measured -0.09 ms per step in a cross-process A/B, profiles/r04_step_tune_ab.txt); its choices
 # replace the table's entries of the same signatures

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export MEBT_GEMM_TUNE_CACHE=$OUT/tune_cache.txt
 for CFG in c4 c5; do
-  ARGS="$ROOT/bench.py --secondary $CFG --no-cpu-baseline"
+  ARGS="$ROOT/bench.py --full --secondary $CFG --no-cpu-baseline"
   cd "$ROOT" && python3 $ARGS > "$OUT/${CFG}_populate.json" 2> "$OUT/${CFG}_populate.err"
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${CFG}_stats" -o bench -- python3 $ARGS > "$OUT/${CFG}_stats.json" 2> "$OUT/${CFG}_stats.err"

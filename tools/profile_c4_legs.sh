@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 for LEG in revise sample bootstrap train; do
-  ARGS="$ROOT/bench.py --secondary c4 --c4-legs $LEG --no-cpu-baseline"
+  ARGS="$ROOT/bench.py --full --secondary c4 --c4-legs $LEG --no-cpu-baseline"
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${LEG}_stats" -o bench -- python3 $ARGS > "$OUT/c4_${LEG}_run.json" 2> "$OUT/c4_${LEG}.err"
   cp "$OUT/${LEG}_stats/"*kernel_stats.csv "$OUT/c4_${LEG}_kernel_stats.csv" 2>/dev/null

@@ -22,7 +22,7 @@ with open(os.path.join(root, "gpurun_out/tune/gfx950_r6_refined.txt"), "w") as f
     f.write(ver + "\n" + "".join(f"{k} {v}\n" for k, v in table.items()))
 print(f"{len(refined)} refined signatures merged ({n} differ from the shipped table); {len(table)} entries")
 PY
-run() { python3 bench.py --steps 30 --warmup 5 --windows 1 --secondary none --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['roofline']['gemm_ms_per_step'])"; }
+run() { python3 bench.py --steps 30 --warmup 5 --full --windows 1 --secondary none --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['roofline']['gemm_ms_per_step'])"; }
 for r in $(seq 1 $R); do
   a=$(run)
   cp gpurun_out/tune/gfx950_r6_refined.txt /tmp/refined_cache.txt
