@@ -319,6 +319,40 @@ int mebt_op_embedding_rows(int32_t dtype, const int64_t* ids, const float* embed
 /* fp32 -> fp16 cast of a flat buffer (n multiple of 4). */
 int mebt_op_cast_f16(const float* src, void* dst, int64_t n, mebt_stream_t stream);
 
+/* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
+ * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
+ * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then
+ * 2 x / 255 - 1 (fvd.py:17-28). */
+int mebt_op_i3d_preprocess(int32_t dtype, const uint8_t* in, void* out, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
+                           mebt_stream_t stream);
+#define MEBT_I3D_MAX_SEGS 3
+/* Output columns [n0, n1) of a convolution go to out[voxel * cstride + coff + (n - n0)] (a slice of a concatenated tensor). */
+typedef struct mebt_i3d_seg {
+    void* out;
+    int32_t n0, n1, cstride, coff;
+} mebt_i3d_seg;
+/* Unit3D (pytorch_i3d.py:50-136) with eval-mode BatchNorm folded into w / bias: an implicit GEMM over K = k0 k1 k2 Cin (flat
+ * (tap, ci) index, ci fastest).  in: contiguous channels-last [B, Ti, Hi, Wi, Cin]; w: [Npad][Kpad] of `dtype`, Npad = Cout rounded
+ * up to 64, Kpad = K rounded up to 32, zero in the padding; bias fp32 [Cout] or NULL; relu 0 / 1.  Zero padding: output voxel o
+ * reads input o * s - pad_front + tap, and the output size must equal (size + pad_front + pad_back - k) / s + 1 on every axis.
+ * nseg (1..3) segments cover [0, Cout) in order; several segments run the 1x1 branches of an Inception module as one GEMM. */
+typedef struct mebt_i3d_conv_desc {
+    const void* in; const void* w; const float* bias;
+    int32_t B, Ti, Hi, Wi, Cin, To, Ho, Wo, Cout;
+    int32_t k[3], s[3], pad_front[3], pad_back[3];
+    int32_t relu;
+    int32_t nseg;
+    mebt_i3d_seg seg[MEBT_I3D_MAX_SEGS];
+} mebt_i3d_conv_desc;
+int mebt_op_i3d_conv(int32_t dtype, const mebt_i3d_conv_desc* d, mebt_stream_t stream);
+/* MaxPool3dSamePadding (pytorch_i3d.py:13-46): zero "same" padding, output [B, ceil(Ti/st), ceil(Hi/sh), ceil(Wi/sw), C]. */
+int mebt_op_i3d_maxpool(int32_t dtype, const void* in, void* out, int32_t B, int32_t Ti, int32_t Hi, int32_t Wi, int32_t C, int32_t kt,
+                        int32_t kh, int32_t kw, int32_t st, int32_t sh, int32_t sw, mebt_stream_t stream);
+/* Head (pytorch_i3d.py:324-331), fp32: AvgPool3d([2, 7, 7], stride 1) of x [B, T, 7, 7, C] into pooled (scratch [B, T - 1, C]),
+ * the logits 1x1x1 convolution (w fp32 [ncls][C], bias fp32 [ncls] or NULL), the mean over time into logits [B, ncls]. */
+int mebt_op_i3d_head(int32_t dtype, const void* x, const float* w, const float* bias, float* pooled, float* logits, int32_t B, int32_t T,
+                     int32_t H, int32_t W, int32_t C, int32_t ncls, mebt_stream_t stream);
+
 /* ---- instrumentation ----------------------------------------------------------------------------- */
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py roofline): enable, run,
  * then read {launches, total ms, total algorithmic flops} of the GEMM family (family 0), or the
