@@ -391,6 +391,16 @@ void mebt_debug_gemm_scratch(void* buf, int64_t bytes);
 /* Diagnostics only: with a device buffer of 4 x 8 bytes per workgroup installed, wave 0 of every workgroup of the plain bf16
  * GEMM kernels stamps s_memtime at entry / first k-tile landed / main loop done / epilogue stores retired (NULL: off). */
 void mebt_debug_gemm_stamps(unsigned long long* buf);
+/* Tests / benchmarking only: mebt_op_attention_fwd / _bwd apply attention dropout with probability p under `seed` (site 0; p = 0:
+ * off, the default).  `dmask` (mebt_op_attention_fwd writes it, _bwd reads it; NULL: every kernel hashes) is a device buffer of
+ * B * H * NQ * 32 * ceil(NK / 256) bytes for the shapes it is used with — the layout the model's training step uses. */
+void mebt_debug_attn_dropout(uint64_t seed, float p, void* dmask);
+/* Benchmarking / tests only: A/B of the bf16 attention launch forms.  bit 0: linear block order instead of the XCD-local one; bit 1:
+ * the backward as two launches (dQ, then dK/dV) instead of one grid.  -1 restores the environment's choice (MEBT_ATTN_LEGACY, 0). */
+void mebt_debug_attn_legacy(int32_t bits);
+/* Tests only: the block order of the MFMA attention grids.  For a 1-D grid of T = X * H * B workgroups (X row blocks, H heads), workgroup
+ * t writes t to pos_to_id[(b * H + h) * X + x] for the (x, h, b) it takes; xcd = 1 the XCD-local order, 0 the linear one. */
+int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int32_t xcd, int32_t* pos_to_id, mebt_stream_t stream);
 /* Diagnostics (tools/wgrad_bench.py): every grouped weight-gradient launch uses this tile (128 or 64 each way) and LDS ring depth
  * (2-4) instead of the tuned / shipped choice; tbm = 0 switches the override off. */
 void mebt_debug_grouped_config(int32_t tbm, int32_t tbn, int32_t ring);

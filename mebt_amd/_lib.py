@@ -93,6 +93,9 @@ PROTOTYPES = {
     "mebt_debug_gemm_scratch": (None, [c_vp, c_i64]),
     "mebt_debug_gemm_stamps": (None, [c_vp]),
     "mebt_debug_grouped_config": (None, [c_i32, c_i32, c_i32]),
+    "mebt_debug_attn_dropout": (None, [C.c_uint64, c_f32, c_vp]),
+    "mebt_debug_attn_legacy": (None, [c_i32]),
+    "mebt_debug_attn_block_order": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mebt_gemm_autotune": (None, [c_i32]),
     "mebt_gemm_autotune_enabled": (c_i32, []),
     "mebt_gemm_tune_export": (c_i64, [C.c_char_p, c_i64]),

@@ -317,6 +317,7 @@ int launch_attn_bwd_mfma(const AttnParams& p, hipStream_t stream);
 #else
 static int launch_attn_fwd_mfma(const AttnParams&, hipStream_t) { return -1; }
 static int launch_attn_bwd_mfma(const AttnParams&, hipStream_t) { return -1; }
+int launch_attn_block_order_probe(int, int, int, int, int32_t*, hipStream_t) { mebt_set_error("built without the MFMA attention"); return MEBT_EINVAL; }
 #endif
 #ifdef MEBT_HAVE_ATTN_MFMA
 static int g_force_generic = 0;
@@ -328,6 +329,13 @@ void mebt_attn_force_generic(int on) { g_force_generic = on; }
 #else
 void mebt_attn_force_generic(int) {}
 #endif
+
+static int g_attn_legacy = -1;
+void mebt_attn_set_legacy(int bits) { g_attn_legacy = bits; }
+int mebt_attn_legacy() {
+    static const int env = [] { const char* e = getenv("MEBT_ATTN_LEGACY"); return e ? atoi(e) : 0; }();
+    return g_attn_legacy >= 0 ? g_attn_legacy : env;
+}
 
 #define DISPATCH_HD(FN, T)                                             \
     switch (p.HD) {                                                    \

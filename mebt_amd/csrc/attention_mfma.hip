@@ -118,6 +118,36 @@ __device__ __forceinline__ float group_max(float v) {
 }
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
+// Block order.  Every launch is a 1-D grid of T = X row blocks x H heads x B samples; the dispatcher deals consecutive workgroup
+// ids round-robin to the 8 XCDs (id & 7), and the row blocks of one (b, h) read the same K / V (Q / dO in dK/dV).  Linear order
+// (x fastest) put them on 2-6 different XCDs, each pulling its own copy through its own L2.  XCD-local order: the ids of XCD c
+// (id & 7 == c) take a contiguous run of the linear order, of length ceil or floor(T / 8) (the remainder scheme of xcd_tile,
+// gemm_kernels.h), so a bijection for any T.  Only the assignment of blocks to ids changes, not what a block computes.
+struct BlockPos { int x, h, b; };
+__device__ __forceinline__ BlockPos attn_block_pos(int t, int T, int X, int H, bool xcd) {
+    int j = t;
+    if (xcd) {
+        const int q = T >> 3, r = T & 7, c = t & 7;
+        j = c * q + min(c, r) + (t >> 3);
+    }
+    BlockPos bp;
+    bp.x = j % X;
+    const int hb = j / X;
+    bp.h = hb % H;
+    bp.b = hb / H;
+    return bp;
+}
+// delta = rowsum(dO o O) of the 16 rows whose fragments a wave holds (lane l: row l & 15, k = 32 ks + 8 (l >> 4) + j).  The dQ role
+// and the dK/dV role of the fused backward both use this: the same sum order, so the same bits.
+__device__ __forceinline__ float row_delta(const bf16x8 (&gf)[2], const bf16x8 (&of)[2]) {
+    float delta = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) delta += (float)gf[ks][j] * (float)of[ks][j];
+    return group_sum(delta);
+}
+
 // ------------------------------------------------------------------------------------------------
 // chunked LDS-DMA staging shared by the three kernels
 // ------------------------------------------------------------------------------------------------
@@ -195,8 +225,9 @@ __global__ __launch_bounds__(NW * SPLIT * 64) void attn_fwd_mfma(const AttnParam
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = SPLIT == 1 ? 0 : wave_all / NW, wave = SPLIT == 1 ? wave_all : wave_all % NW;
     char* smem = smem_all + half * (NST * SBYTES);
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int q = blockIdx.x * (NW * 16) + wave * 16 + (lane & 15);
+    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + NW * 16 - 1) / (NW * 16), p.H, p.xcd_order);
+    const int b = bp.b, h = bp.h;
+    const int q = bp.x * (NW * 16) + wave * 16 + (lane & 15);
     const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
     const bool gather = p.kidx != nullptr;          // keys / values = rows kidx[b, :] of a cache of kidx_rows positions per sample
     const int krows = gather ? p.kidx_rows : p.NK;
@@ -398,8 +429,9 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wave_all >> 2, wave = wave_all & 3;
     char* smem = smem_all + half * (2 * SBYTES);
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int q = blockIdx.x * (NW * 16) + wave * 16 + (lane & 15);
+    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + NW * 16 - 1) / (NW * 16), p.H, p.xcd_order);
+    const int b = bp.b, h = bp.h;
+    const int q = bp.x * (NW * 16) + wave * 16 + (lane & 15);
     const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
     const bool gather = p.kidx != nullptr;
     const int krows = gather ? p.kidx_rows : p.NK;
@@ -591,14 +623,12 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// backward: dQ (+ delta = rowsum(dO * O)).  One wave = 16 query rows; K/V chunks streamed.
+// backward: dQ (+ delta = rowsum(dO * O)).  One wave = 16 query rows; K/V chunks streamed.  Row block xb of (b, h).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVES * 64) void attn_bwd_dq_mfma(const AttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+__device__ __forceinline__ void bwd_dq_block(const AttnParams& p, char* smem, int xb, int h, int b) {
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int q = blockIdx.x * BLOCK_ROWS + wave * 16 + (lane & 15);
+    const int q = xb * BLOCK_ROWS + wave * 16 + (lane & 15);
     const bool qv = q < p.NQ;
     const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
     const bf16_t* G = reinterpret_cast<const bf16_t*>(p.d_o) + (size_t)b * p.NQ * p.lddo + h * 64;
@@ -627,7 +657,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dq_mfma(const AttnParams 
     const int mtiles = mebt_attn_dmask_tiles(p.NK);
     const size_t mrow0 = ((size_t)b * p.H + h) * p.NQ;
     const __amdgpu_buffer_rsrc_t rmask = make_rsrc(p.dmask ? p.dmask + mrow0 * mtiles * 4 : (const uint16_t*)p.q, use_bits ? (size_t)p.NQ * mtiles * 8 : 0);
-    const uint32_t moff = (uint32_t)((blockIdx.x * BLOCK_ROWS + 32 * (wave & 3) + (lane >> 1)) * mtiles * 8 + (lane & 1) * 16);
+    const uint32_t moff = (uint32_t)((xb * BLOCK_ROWS + 32 * (wave & 3) + (lane >> 1)) * mtiles * 8 + (lane & 1) * 16);
     auto issue_mask = [&](char* stage, int chunk) {
         if (wave < 4) dma16(rmask, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * 32);
     };
@@ -639,12 +669,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dq_mfma(const AttnParams 
         lv.issue(smem + STAGE_BYTES + CHUNK_BYTES, 1, wave);
         issue_mask(smem + STAGE_BYTES, 1);
     }
-    float delta = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) delta += (float)gf[ks][j] * (float)of[ks][j];
-    delta = group_sum(delta);
+    const float delta = row_delta(gf, of);
     const float lse2 = lse_q * LOG2E;
     const float c = 0.125f * LOG2E;
     FragOffsets fo;
@@ -720,16 +745,20 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dq_mfma(const AttnParams 
 }
 
 // ------------------------------------------------------------------------------------------------
-// backward: dK, dV.  One wave = 16 key rows; Q / dO chunks (+ lse, delta) streamed.
+// backward: dK, dV.  One wave = 16 key rows; Q / dO chunks (+ lse, delta) streamed.  Row block xb of (b, h).
+// OWN_DELTA: delta = rowsum(dO o O) of a chunk's queries is computed here (row_delta, as the dQ role does) instead of being read from
+// the dQ kernel's output, so that the two can run in one grid.  Each wave sums 32 of the chunk's rows from fragments loaded straight
+// from global memory, issued before the chunk's DMA (so the counted waits below still see only DMA behind them), and parks the sums
+// in the chunk's delta vector in LDS.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <bool OWN_DELTA>
+__device__ __forceinline__ void bwd_dkv_block(const AttnParams& p, char* smem, int xb, int h, int b) {
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.z, h = blockIdx.y;
-    const int key = blockIdx.x * BLOCK_ROWS + wave * 16 + (lane & 15);
+    const int key = xb * BLOCK_ROWS + wave * 16 + (lane & 15);
     const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
     const bf16_t* G = reinterpret_cast<const bf16_t*>(p.d_o) + (size_t)b * p.NQ * p.lddo + h * 64;
+    const bf16_t* Oo = reinterpret_cast<const bf16_t*>(p.o) + (size_t)b * p.NQ * p.ldo + h * 64;
     const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * p.NK * p.ldk + h * 64;
     const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * p.NK * p.ldv + h * 64;
     const float* L = p.lse + ((size_t)b * p.H + h) * p.NQ;
@@ -737,7 +766,8 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
     ChunkDma<> lq, lg;
     lq.init(Q, p.NQ, p.ldq, wave, lane);
     lg.init(G, p.NQ, p.lddo, wave, lane);
-    // lse / delta of a chunk: 256 floats = one 1-KiB piece each, copied by waves 0 and 1 (zero beyond NQ)
+    // lse / delta of a chunk: 256 floats = one 1-KiB piece each, copied by waves 0 and 1 (zero beyond NQ); OWN_DELTA: lse only
+    constexpr int NSTAT = OWN_DELTA ? 1 : 2;
     const __amdgpu_buffer_rsrc_t rstat = make_rsrc(wave == 0 ? L : Dl, (size_t)p.NQ * 4);
     const int nchunks = (p.NQ + CHUNK - 1) / CHUNK;
     // keep bits of (the chunk's 256 queries) x (this workgroup's 2 key tiles): 16 B per query = 4 KiB per chunk = four 1-KiB DMA
@@ -746,11 +776,11 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
     const int mtiles = mebt_attn_dmask_tiles(p.NK);
     const size_t mrow0 = ((size_t)b * p.H + h) * p.NQ;
     const __amdgpu_buffer_rsrc_t rmask = make_rsrc(p.dmask ? p.dmask + mrow0 * mtiles * 4 : (const uint16_t*)p.q, use_bits ? (size_t)p.NQ * mtiles * 8 : 0);
-    const uint32_t moff = (uint32_t)((64 * (wave & 3) + lane) * mtiles * 8 + blockIdx.x * 16);
+    const uint32_t moff = (uint32_t)((64 * (wave & 3) + lane) * mtiles * 8 + xb * 16);
     auto issue = [&](char* stage, int chunk) {
         lq.issue(stage, chunk, wave);
         lg.issue(stage + CHUNK_BYTES, chunk, wave);
-        if (wave < 2) dma16(rstat, lds_addr_of(stage + 2 * CHUNK_BYTES + wave * STAT_BYTES), (uint32_t)(chunk * CHUNK * 4 + lane * 16));
+        if (wave < NSTAT) dma16(rstat, lds_addr_of(stage + 2 * CHUNK_BYTES + wave * STAT_BYTES), (uint32_t)(chunk * CHUNK * 4 + lane * 16));
         if (wave < 4) dma16(rmask, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * CHUNK * (uint32_t)mtiles * 8);
     };
     bf16x8 kf[2], vf[2];
@@ -759,8 +789,38 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
         kf[ks] = frag_global(K, key, p.NK, p.ldk, ks, lane);
         vf[ks] = frag_global(V, key, p.NK, p.ldv, ks, lane);
     }
-    issue(smem, 0);
-    if (nchunks > 1) issue(smem + STAGE_BYTES, 1);
+    // OWN_DELTA: this wave's rows of a chunk are 32 wave + 16 j + (lane & 15), j = 0, 1
+    auto load_delta_rows = [&](bf16x8 (&df)[2][2][2], int chunk) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int row = chunk * CHUNK + 32 * wave + 16 * j + (lane & 15);
+                df[j][0][ks] = frag_global(G, row, p.NQ, p.lddo, ks, lane);
+                df[j][1][ks] = frag_global(Oo, row, p.NQ, p.ldo, ks, lane);
+            }
+    };
+    auto store_delta = [&](const bf16x8 (&df)[2][2][2], char* stage) {
+        float* cd = reinterpret_cast<float*>(stage + 2 * CHUNK_BYTES + STAT_BYTES);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float d = row_delta(df[j][0], df[j][1]);
+            if (g == 0) cd[32 * wave + 16 * j + (lane & 15)] = d;
+        }
+    };
+    if (OWN_DELTA) {
+        bf16x8 d0[2][2][2], d1[2][2][2];
+        load_delta_rows(d0, 0);
+        if (nchunks > 1) load_delta_rows(d1, 1);
+        issue(smem, 0);
+        if (nchunks > 1) issue(smem + STAGE_BYTES, 1);
+        store_delta(d0, smem);
+        if (nchunks > 1) store_delta(d1, smem + STAGE_BYTES);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // written before the barrier that publishes the chunk
+    } else {
+        issue(smem, 0);
+        if (nchunks > 1) issue(smem + STAGE_BYTES, 1);
+    }
     const float c = 0.125f * LOG2E;
     FragOffsets fo;
     fo.init(lane);
@@ -772,7 +832,7 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
     for (int ch = 0; ch < nchunks; ++ch) {
         char* stage = smem + (ch & 1) * STAGE_BYTES;
         if (ch + 1 < nchunks) {
-            if (wave < 2) wait_vm<DMA_PER_WAVE + 2>(); else if (wave < 4) wait_vm<DMA_PER_WAVE + 1>(); else wait_vm<DMA_PER_WAVE>();
+            if (wave < NSTAT) wait_vm<DMA_PER_WAVE + 2>(); else if (wave < 4) wait_vm<DMA_PER_WAVE + 1>(); else wait_vm<DMA_PER_WAVE>();
         } else {
             wait_vm<0>();
         }
@@ -830,7 +890,15 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
         }
         if (ch + 2 < nchunks) {
             __builtin_amdgcn_s_barrier();
-            issue(stage, ch + 2);
+            if (OWN_DELTA) {
+                bf16x8 d2[2][2][2];
+                load_delta_rows(d2, ch + 2);
+                issue(stage, ch + 2);
+                store_delta(d2, stage);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            } else {
+                issue(stage, ch + 2);
+            }
         }
     }
     if (key < p.NK) {
@@ -844,7 +912,48 @@ __global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams
     }
 }
 
+__global__ __launch_bounds__(WAVES * 64) void attn_bwd_dq_mfma(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.xcd_order);
+    bwd_dq_block(p, smem, bp.x, bp.h, bp.b);
+}
+__global__ __launch_bounds__(WAVES * 64) void attn_bwd_dkv_mfma(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NK + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.xcd_order);
+    bwd_dkv_block<false>(p, smem, bp.x, bp.h, bp.b);
+}
+// The whole backward in one grid: the first Tk workgroups are dK/dV blocks (the longer ones, dispatched first), the rest dQ blocks.
+// No role reads what the other writes (dK/dV computes its own delta), so no ordering between them is needed.  Each role's blocks
+// are ordered on their own (attn_block_pos over the role's ids); an offset of the role's first id only relabels the XCDs.
+__global__ __launch_bounds__(WAVES * 64) void attn_bwd_mfma(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int xk = (p.NK + BLOCK_ROWS - 1) / BLOCK_ROWS, tk = xk * p.H * p.B;
+    const int t = blockIdx.x;
+    if (t < tk) {
+        const BlockPos bp = attn_block_pos(t, tk, xk, p.H, p.xcd_order);
+        bwd_dkv_block<true>(p, smem, bp.x, bp.h, bp.b);
+    } else {
+        const BlockPos bp = attn_block_pos(t - tk, gridDim.x - tk, (p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.xcd_order);
+        bwd_dq_block(p, smem, bp.x, bp.h, bp.b);
+    }
+}
+
+// Tests only (mebt_debug_attn_block_order): workgroup t of a T-block grid writes its id at the linear position its (x, h, b) has.
+__global__ void attn_block_order_probe(int T, int X, int H, int xcd, int32_t* pos_to_id) {
+    if (threadIdx.x) return;
+    const BlockPos bp = attn_block_pos(blockIdx.x, T, X, H, xcd);
+    if (bp.x < 0 || bp.x >= X || bp.h < 0 || bp.h >= H || bp.b < 0 || bp.b >= T / (X * H)) return;     // out of range: left unwritten
+    pos_to_id[((size_t)bp.b * H + bp.h) * X + bp.x] = (int32_t)blockIdx.x;
+}
+
 }  // namespace
+
+int launch_attn_block_order_probe(int T, int X, int H, int xcd, int32_t* pos_to_id, hipStream_t stream) {
+    if (T <= 0 || X <= 0 || H <= 0 || T % (X * H)) { mebt_set_error("attention block order: T must be a positive multiple of X * H"); return MEBT_ESHAPE; }
+    hipLaunchKernelGGL(attn_block_order_probe, dim3(T), dim3(64), 0, stream, T, X, H, xcd, pos_to_id);
+    MEBT_HIP_CHECK(hipGetLastError());
+    return MEBT_OK;
+}
 
 static int check_layout(const AttnParams& p) {
     if (p.HD != 64) { mebt_set_error("mfma attention: head size must be 64"); return MEBT_ESHAPE; }
@@ -860,6 +969,7 @@ static int check_layout(const AttnParams& p) {
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_pp), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
+        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
         inited = true;
     }
     return MEBT_OK;
@@ -871,6 +981,7 @@ int launch_attn_fwd_mfma(const AttnParams& p_in, hipStream_t stream) {
     AttnParams p = p_in;
     drop_mark_small(p.drop, (uint64_t)p.B * p.H * p.NQ * p.NK);
     if (int rc = check_layout(p)) return rc;
+    p.xcd_order = !(mebt_attn_legacy() & 1);
     // 128-row workgroups (8 waves) unless their grid leaves CUs idle; then 64-row workgroups (4 waves, twice the workgroups).
     // MEBT_ATTN_FWD_WAVES = 4 | 8 forces one form (A/B runs).
     static const int force = [] { const char* e = getenv("MEBT_ATTN_FWD_WAVES"); return e ? atoi(e) : 0; }();
@@ -881,17 +992,17 @@ int launch_attn_fwd_mfma(const AttnParams& p_in, hipStream_t stream) {
     const int xl = p.kidx ? ((p.NK * 4 + 15) & ~15) : 0;       // the key index list of a sample, staged behind the rings
     if (xl && xl + 4 * CHUNK_BYTES > 160 * 1024) { mebt_set_error("mfma attention: a gathered key set holds at most 8192 keys"); return MEBT_ESHAPE; }
     if (four) {
-        const dim3 grid((p.NQ + 63) / 64, p.H, p.B);
+        const dim3 grid((p.NQ + 63) / 64 * p.H * p.B);
         // short key sets: two stages of 128 keys (64 KiB: two workgroups per CU); long ones: four stages, one workgroup per CU
         static const int split_on = [] { const char* e = getenv("MEBT_ATTN_FWD_SPLIT"); return e ? atoi(e) : 1; }();
         if (p.NK <= 1024) hipLaunchKernelGGL((attn_fwd_mfma<4, 2>), grid, dim3(256), 2 * CHUNK_BYTES + xl, stream, p);
-        else if (split_on && (long)grid.x * p.H * p.B <= 256) {    // one workgroup per CU at most: a second group of waves per query block
+        else if (split_on && (long)grid.x <= 256) {    // one workgroup per CU at most: a second group of waves per query block
             if (split_on == 2) hipLaunchKernelGGL((attn_fwd_mfma<4, 2, 2>), grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);   // both groups in phase (A/B)
             else hipLaunchKernelGGL(attn_fwd_pp, grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);
         }
         else hipLaunchKernelGGL((attn_fwd_mfma<4, 4>), grid, dim3(256), 4 * CHUNK_BYTES + xl, stream, p);
     } else {
-        const dim3 grid((p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.B);
+        const dim3 grid((p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS * p.H * p.B);
         if (p.NK <= CHUNK) hipLaunchKernelGGL((attn_fwd_mfma<8, 1>), grid, dim3(WAVES * 64), 2 * CHUNK_BYTES + xl, stream, p);
         else hipLaunchKernelGGL((attn_fwd_mfma<8, 2>), grid, dim3(WAVES * 64), 2 * 2 * CHUNK_BYTES + xl, stream, p);
     }
@@ -904,10 +1015,15 @@ int launch_attn_bwd_mfma(const AttnParams& p_in, hipStream_t stream) {
     drop_mark_small(p.drop, (uint64_t)p.B * p.H * p.NQ * p.NK);
     if (int rc = check_layout(p)) return rc;
     if ((p.lddo | p.lddq | p.lddk | p.lddv) % 8) { mebt_set_error("mfma attention: row strides must be multiples of 8 elements"); return MEBT_ESHAPE; }
-    const dim3 gq((p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.B);
-    hipLaunchKernelGGL(attn_bwd_dq_mfma, gq, dim3(WAVES * 64), lds_bytes(p.NK), stream, p);
-    const dim3 gk((p.NK + BLOCK_ROWS - 1) / BLOCK_ROWS, p.H, p.B);
-    hipLaunchKernelGGL(attn_bwd_dkv_mfma, gk, dim3(WAVES * 64), lds_bytes(p.NQ), stream, p);
+    const int legacy = mebt_attn_legacy();
+    p.xcd_order = !(legacy & 1);
+    const int tq = (p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS * p.H * p.B, tk = (p.NK + BLOCK_ROWS - 1) / BLOCK_ROWS * p.H * p.B;
+    if (legacy & 2) {       // dQ (writes delta), then dK/dV (reads it)
+        hipLaunchKernelGGL(attn_bwd_dq_mfma, dim3(tq), dim3(WAVES * 64), lds_bytes(p.NK), stream, p);
+        hipLaunchKernelGGL(attn_bwd_dkv_mfma, dim3(tk), dim3(WAVES * 64), lds_bytes(p.NQ), stream, p);
+    } else {                // one grid, both roles: the LDS of the larger
+        hipLaunchKernelGGL(attn_bwd_mfma, dim3(tk + tq), dim3(WAVES * 64), max(lds_bytes(p.NK), lds_bytes(p.NQ)), stream, p);
+    }
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

@@ -81,6 +81,19 @@ extern "C" int mebt_op_layernorm_bwd(int32_t dtype, const void* x, const void* d
     return launch_ln_bwd(p, dtype, S(stream));
 }
 
+// operator-level attention dropout (mebt_debug_attn_dropout): off unless set
+static DropCfg g_op_attn_drop = make_drop(0, 0, 0.f);
+static uint16_t* g_op_attn_dmask = nullptr;
+extern "C" void mebt_debug_attn_dropout(uint64_t seed, float p, void* dmask) {
+    g_op_attn_drop = make_drop(seed, SITE_ATTN, p);
+    g_op_attn_dmask = p > 0.f ? (uint16_t*)dmask : nullptr;
+}
+extern "C" void mebt_debug_attn_legacy(int32_t bits) { mebt_attn_set_legacy(bits); }
+extern "C" int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int32_t xcd, int32_t* pos_to_id, mebt_stream_t stream) {
+    if (!pos_to_id) { mebt_set_error("attention block order: null pointer"); return MEBT_EINVAL; }
+    return launch_attn_block_order_probe(T, X, H, xcd, pos_to_id, S(stream));
+}
+
 extern "C" int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
                                      int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
                                      int32_t ldo, int32_t force_generic, mebt_stream_t stream) {
@@ -90,6 +103,7 @@ extern "C" int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k
     memset(&p, 0, sizeof(p));
     p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse; p.B = B; p.H = H; p.NQ = NQ; p.NK = NK; p.HD = HD;
     p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+    p.drop = g_op_attn_drop; p.dmask = g_op_attn_dmask;
     mebt_attn_force_generic(force_generic);
     const int rc = launch_attn_fwd(p, dtype, S(stream));
     mebt_attn_force_generic(0);
@@ -107,6 +121,7 @@ extern "C" int mebt_op_attention_bwd(int32_t dtype, const void* q, const void* k
     p.q = q; p.k = k; p.v = v; p.o = const_cast<void*>(o); p.lse = const_cast<float*>(lse); p.B = B; p.H = H; p.NQ = NQ; p.NK = NK; p.HD = HD;
     p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
     p.d_o = d_o; p.dq = dq; p.dk = dk; p.dv = dv; p.delta = delta; p.lddo = ldo; p.lddq = ldq; p.lddk = ldk; p.lddv = ldv;
+    p.drop = g_op_attn_drop; p.dmask = g_op_attn_dmask;
     mebt_attn_force_generic(force_generic);
     const int rc = launch_attn_bwd(p, dtype, S(stream));
     mebt_attn_force_generic(0);

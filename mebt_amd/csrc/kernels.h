@@ -231,12 +231,19 @@ struct AttnParams {
     // kidx[b * NK + r] of a buffer that holds `kidx_rows` rows per sample (k, v point at sample 0, position 0).  NK <= 8192.
     const int32_t* kidx = nullptr;
     int kidx_rows = 0;
+    // MFMA kernels, set by their launchers: 1 = XCD-local block order (attn_block_pos), 0 = linear (x fastest, then head, batch)
+    int xcd_order = 0;
 };
 __host__ __device__ static inline int mebt_attn_dmask_tiles(int NK) { return 4 * ((NK + 255) / 256); }
 static inline size_t mebt_attn_dmask_bytes(int B, int H, int NQ, int NK) { return (size_t)B * H * NQ * mebt_attn_dmask_tiles(NK) * 8; }
 int launch_attn_fwd(const AttnParams& p, int dtype, hipStream_t stream);
 int launch_attn_bwd(const AttnParams& p, int dtype, hipStream_t stream);
 void mebt_attn_force_generic(int on);
+// A/B of the MFMA attention launch forms (mebt_debug_attn_legacy, MEBT_ATTN_LEGACY read once): bit 0 = linear block order,
+// bit 1 = the backward as two launches (dQ, then dK/dV reading dQ's delta); -1 = back to the environment's choice (default 0)
+void mebt_attn_set_legacy(int bits);
+int mebt_attn_legacy();
+int launch_attn_block_order_probe(int T, int X, int H, int xcd, int32_t* pos_to_id, hipStream_t stream);   // tests only
 bool attn_fwd_can_gather(int dtype, int HD);     // the forward of this (dtype, head size) honours AttnParams::kidx
 
 // ---- sampler (reference transformer.py:826-910, :413-439, mask_sampler.py:178-246) -----------------
