@@ -319,6 +319,15 @@ int mebt_op_embedding_rows(int32_t dtype, const int64_t* ids, const float* embed
 /* fp32 -> fp16 cast of a flat buffer (n multiple of 4). */
 int mebt_op_cast_f16(const float* src, void* dst, int64_t n, mebt_stream_t stream);
 
+/* ---- frame ingest for pixel-space training (reference mebt/data.py FrameListDataset.getTensor) ------------------------------
+ * Uint8 RGB frames [N, Hs, Ws, 3] (N = clips x T) -> crop [y0, y0 + S) x [x0, x0 + S) -> PIL Image.resize((R, R), BILINEAR) ->
+ * float32(u) / 255 - 0.5 through `lut` [256] -> out [Bout, 3, T, R, R] fp32; clip i goes to slot slots[i] (NULL: slot i, a slot
+ * outside [0, Bout) is skipped).  `tab` = xmin[R], n[R], k[R][K] int32: Pillow's fixed-point coefficients of the S -> R axis
+ * (mebt_amd/frames.py:axis_coeffs), used for both axes; `rows` output rows per workgroup, whose source rows (at most `span`)
+ * fit the LDS.  S == R: no resampling, `tab` may be NULL.  Integer arithmetic only: the result equals PIL's bit for bit. */
+int mebt_op_frames_to_video(const uint8_t* frames, float* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
+                            int32_t S, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const float* lut,
+                            const int32_t* slots, int32_t Bout, mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

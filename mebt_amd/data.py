@@ -3,7 +3,13 @@
 and the sharding `VideoData._dataloader` gets from `DistributedSampler` (:271-292).  Token files are `.npz` (or HDF5
 when h5py is installed) with the reference's keys: `{train,test}_data` [frames,H,W] and `{train,test}_idx` (start frame
 of every video plus a trailing sentinel).  Random draws use torch's global generator with the same calls in the same
-order as the reference, so a seeded run picks the same clips, crops and permutations."""
+order as the reference, so a seeded run picks the same clips, crops and permutations.
+
+The frame-folder branch (`image_folder`, FrameListDataset, VideoData) sits at the end of the module."""
+import functools
+import os
+import random
+
 import numpy as np
 import torch
 
@@ -163,3 +169,161 @@ class TokenData:
         parser.add_argument('--stft_data', action='store_true')
         parser.add_argument('--preprocessed_hdf5', action='store_true')
         return parser
+
+
+# ---- pixel-space data: the reference's `image_folder` branch (mebt/data.py:419-521) --------------------------------------
+IMG_EXTENSIONS = ['.jpg', '.JPG', '.jpeg', '.JPEG', '.png', '.PNG']
+
+
+def is_image_file(filename):
+    return any(filename.endswith(extension) for extension in IMG_EXTENSIONS)
+
+
+def _open_rgb(path):
+    from PIL import Image
+    img = Image.open(path)
+    if img.mode != "RGB":       # the reference would fail later, in the first stage's 3-channel convolution
+        raise ValueError(f"{path}: frame mode {img.mode!r}, the frame datasets take 8-bit RGB images only (convert them to RGB)")
+    return img
+
+
+class FrameListDataset(torch.utils.data.Dataset):
+    """reference FrameListDataset (data.py:431-521): frames `[VIDEO_ID]_[FRAME_NUM].png` listed in `data_folder`/train.txt or
+    test.txt.  Items are {'video' float32 [3, T, R, R] in [-0.5, 0.5], 'indices' randperm(prod(latent_shape))}, made with the
+    same random calls in the same order (`random.randint` for the start frame, then torch's randperm).
+
+    raw=True: the same random calls, but no crop / resize / normalisation: 'video' is the decoded uint8 [T, Hs, Ws, 3] at the
+    source size, for the GPU ingest (mebt_amd/frames.py, collate with `frames.collate_raw`)."""
+
+    def load_video_frames(self, dataroot):
+        list_file = os.path.join(dataroot, 'train.txt' if self.train else 'test.txt')
+        with open(list_file, "r") as f:
+            paths = f.read().splitlines()
+        paths = sorted(paths)                       # string order: v_10.png before v_2.png (a break starts a new video)
+        data_all = []
+        video_id = ''
+        video_frames = []
+        last_frame = 0
+        cnt = 0
+        for path in paths:
+            file_name = path.split('/')[-1]
+            cur_video = ''.join(path.split('/')[:-1]) + ''.join(file_name.split('_')[:-1])
+            cur_frame = int(file_name.split('_')[-1].split('.')[0])     # parsed before the extension check, as the reference does
+            if video_id != cur_video or cur_frame != (last_frame + 1):
+                if video_id == cur_video and cur_frame != (last_frame + 1):
+                    cnt += 1
+                video_id = cur_video
+                if len(video_frames) > 0:
+                    if len(video_frames) >= max(0, self.sequence_length * self.sample_every_n_frames):
+                        data_all.append(video_frames)
+                    video_frames = []
+            if is_image_file(path):
+                video_frames.append(path)
+            last_frame = cur_frame
+        # the last video of the list is never flushed (reference behaviour)
+        self.video_num = len(data_all)
+        self.discontinuities = cnt
+        print(f"Total num of videos: {self.video_num}")
+        print(f"Total num of discontinuous videos: {cnt}")
+        return data_all
+
+    def __init__(self, data_folder, sequence_length, resolution=64, sample_every_n_frames=1, train=True, latent_shape=[],
+                 raw=False):
+        self.resolution = resolution
+        self.sequence_length = sequence_length
+        self.sample_every_n_frames = sample_every_n_frames
+        self.train = train
+        self.raw = raw
+        self.data_all = self.load_video_frames(data_folder)
+        self.latent_shape = latent_shape
+
+    n_classes = 0
+
+    def __getitem__(self, index):
+        batch_data = self.getTensor(index)
+        return {'video': batch_data, 'indices': torch.randperm(int(np.prod(self.latent_shape)))}
+
+    def _clip_range(self, video_len):
+        if self.sequence_length == -1:              # the whole video
+            assert self.sample_every_n_frames == 1
+            return 0, video_len
+        n_frames_interval = self.sequence_length * self.sample_every_n_frames
+        start_idx = random.randint(0, video_len - n_frames_interval)
+        return start_idx, start_idx + n_frames_interval
+
+    def getTensor(self, index):
+        from PIL import Image
+        video = self.data_all[index]
+        start_idx, end_idx = self._clip_range(len(video))
+        img = _open_rgb(video[0])
+        h, w = img.height, img.width
+        if h > w:
+            half = (h - w) // 2
+            cropsize = (0, half, w, half + w)       # left, upper, right, lower
+        elif w > h:
+            half = (w - h) // 2
+            cropsize = (half, 0, half + h, h)
+        images = []
+        for i in range(start_idx, end_idx, self.sample_every_n_frames):
+            img = _open_rgb(video[i])
+            if self.raw:
+                if (img.height, img.width) != (h, w):
+                    raise ValueError(f"{video[i]}: {img.height}x{img.width} frame in a clip of {h}x{w} frames")
+                images.append(np.asarray(img, dtype=np.uint8))
+                continue
+            if h != w:
+                img = img.crop(cropsize)
+            if h != self.resolution or w != self.resolution:       # the uncropped size decides, as in the reference
+                img = img.resize((self.resolution, self.resolution), Image.BILINEAR)
+            img = np.asarray(img, dtype=np.float32)
+            img /= 255.
+            images.append(torch.from_numpy(img - 0.5).unsqueeze(0))
+        if self.raw:
+            return torch.from_numpy(np.stack(images))
+        return torch.cat(images).permute(3, 0, 1, 2)
+
+    def __len__(self):
+        return self.video_num
+
+
+def _arg(a, k, d):
+    return a[k] if (hasattr(a, "__contains__") and k in a) else getattr(a, k, d)
+
+
+class VideoData(TokenData):
+    """reference VideoData._dataset (data.py:248-273): `vtokens` -> token clips (TokenClipDataset, in latent units as the
+    launcher passes them), `image_folder` -> FrameListDataset (in pixel units).  raw=True makes the frame loader return
+    uint8 source-size clips collated by `frames.collate_raw` for the GPU ingest."""
+
+    def __init__(self, args, shuffle=True, world_size=1, rank=0, raw=False):
+        super().__init__(args, shuffle=shuffle, world_size=world_size, rank=rank)
+        self.raw = raw
+
+    def _dataset(self, train):
+        a = self.args
+        if _arg(a, "vtokens", False):
+            return super()._dataset(train)
+        if _arg(a, "image_folder", False):
+            return FrameListDataset(_arg(a, "data_path", None), _arg(a, "sequence_length", 16), resolution=_arg(a, "resolution", 128),
+                                    sample_every_n_frames=_arg(a, "sample_every_n_frames", 1), train=train,
+                                    latent_shape=_arg(a, "latent_shape", [1]), raw=self.raw)
+        if _arg(a, "preprocessed_hdf5", False):
+            raise NotImplementedError("HDF5Dataset_preprocessed (preprocessed_hdf5: True) is not available: it needs h5py and "
+                                      "pixel-space HDF5 files; use image_folder: True with a frame folder, or vtokens: True")
+        raise NotImplementedError("VideoDataset (video files, the reference's default branch) is not available: it needs "
+                                  "torchvision's VideoClips; use image_folder: True with a frame folder, or vtokens: True")
+
+    def _dataloader(self, train):
+        ds = self._dataset(train)
+        if not isinstance(ds, FrameListDataset):
+            return super()._dataloader(train)
+        a = self.args
+        sampler = ShardedSampler(len(ds), self.world_size, self.rank) if self.world_size > 1 else None
+        nw = _arg(a, "num_workers", 0)
+        collate = None
+        if self.raw:
+            from .frames import collate_raw
+            collate = functools.partial(collate_raw, resolution=ds.resolution)
+        return torch.utils.data.DataLoader(ds, batch_size=_arg(a, "batch_size", 6), num_workers=nw, pin_memory=True, sampler=sampler,
+                                           shuffle=sampler is None and self.shuffle, persistent_workers=bool(train and nw > 0),
+                                           collate_fn=collate)

@@ -1,0 +1,235 @@
+"""Frame ingest: uint8 RGB frames -> the reference's float clip [B, 3, T, R, R], on the GPU.
+
+The reference prepares every frame with PIL in its DataLoader workers (mebt/data.py FrameListDataset.getTensor): center
+crop to the shorter side (the box comes from the clip's first frame), `Image.resize((R, R), Image.BILINEAR)`, then
+`np.float32(u) / 255. - 0.5`.  Here the workers only decode (`FrameListDataset(raw=True)`) and the crop, the resize and the
+normalisation run in one HIP kernel (csrc/frames/frames.hip, `mebt_op_frames_to_video`) that is bit-identical to PIL.
+
+Pillow's 8-bit resampler (Resample.c) is integer arithmetic once its coefficients are fixed, so the host builds them exactly
+as Pillow does and the kernel only multiplies and adds int32:
+
+  per axis, in -> out:  scale = in / out, fs = max(scale, 1), support = fs (triangle filter of support 1), ss = 1 / fs
+  output xx:            center = (xx + 0.5) * scale
+                        xmin = max(int(center - support + 0.5), 0), n = min(int(center + support + 0.5), in) - xmin
+                        w_x = tri((x + xmin - center + 0.5) * ss), x < n;  w /= sum(w) (double);  k = int(0.5 + w * 2**22)
+  two passes, horizontal first, each: acc = 1 << 21; acc += sum(k * px) (int32); px' = clamp(acc >> 22, 0, 255) (uint8)
+
+A same-size resize is a copy (the tables degenerate to one weight of 2**22).  The crop is square, so one table serves both
+axes.  `resize_twin` is the numpy statement of the same algorithm: the documented definition the tests hold the tables to
+(against PIL) and the kernel to; the product never computes frames on the CPU.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+PRECISION_BITS = 22                         # Pillow: 32 - 8 (pixel) - 2 (headroom)
+MAX_LDS_BYTES = 60 * 1024                   # dynamic LDS of one workgroup: uint8 rows of the horizontal pass (FR_MAX_LDS)
+MAX_TILE_ROWS = 16                          # output rows per workgroup
+
+
+def _tri(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def axis_coeffs(n_in, n_out):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter: (xmin [n_out], n [n_out], k [n_out, K])
+    int32, K = the widest window; taps past n have weight 0 and are never read."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ss = 1.0 / fs
+    K = int(math.ceil(support)) * 2 + 1
+    xmin = np.zeros(n_out, np.int32)
+    cnt = np.zeros(n_out, np.int32)
+    k = np.zeros((n_out, K), np.int32)
+    for xx in range(n_out):
+        center = (xx + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        hi = min(int(center + support + 0.5), n_in)
+        w = [_tri((x + lo - center + 0.5) * ss) for x in range(hi - lo)]
+        tot = sum(w)
+        for x in range(hi - lo):
+            wx = w[x] / tot if tot != 0.0 else w[x]
+            k[xx, x] = int(-0.5 + wx * (1 << PRECISION_BITS)) if wx < 0 else int(0.5 + wx * (1 << PRECISION_BITS))
+        xmin[xx], cnt[xx] = lo, hi - lo
+    K = max(1, int(cnt.max()))
+    return xmin, cnt, np.ascontiguousarray(k[:, :K])
+
+
+def crop_box(h, w):
+    """the reference's center crop of an h x w frame: (y0, x0, side); h == w is no crop"""
+    if h > w:
+        return (h - w) // 2, 0, w
+    if w > h:
+        return 0, (w - h) // 2, h
+    return 0, 0, h
+
+
+def norm_table():
+    """uint8 -> float32 exactly as the reference computes it: np.float32(u) / 255. then - 0.5, both in float32"""
+    t = np.arange(256, dtype=np.float32)
+    t /= 255.
+    return t - 0.5
+
+
+def _pass(src, xmin, cnt, k, axis):
+    """one Pillow pass along `axis` of an [H, W, C] uint8 image"""
+    src = np.moveaxis(src, axis, 0).astype(np.int64)
+    out = np.empty((len(xmin),) + src.shape[1:], np.int64)
+    for i in range(len(xmin)):
+        n = int(cnt[i])
+        acc = np.full(src.shape[1:], 1 << (PRECISION_BITS - 1), np.int64)
+        acc += np.tensordot(k[i, :n].astype(np.int64), src[xmin[i]:xmin[i] + n], axes=(0, 0))
+        out[i] = acc
+    out = np.clip(out >> PRECISION_BITS, 0, 255).astype(np.uint8)
+    return np.moveaxis(out, 0, axis)
+
+
+def resize_twin(img, R):
+    """numpy twin of `Image.resize((R, R), BILINEAR)` on a square uint8 [S, S, 3] image (tests only)"""
+    S = img.shape[0]
+    if img.shape[0] == R and img.shape[1] == R:
+        return img.copy()
+    xmin, cnt, k = axis_coeffs(S, R)
+    xmin_w, cnt_w, k_w = axis_coeffs(img.shape[1], R)
+    return _pass(_pass(img, xmin_w, cnt_w, k_w, 1), xmin, cnt, k, 0)
+
+
+def clip_twin(frames, R):
+    """numpy twin of the whole ingest of one clip: uint8 [T, Hs, Ws, 3] -> float32 [3, T, R, R] (tests only)"""
+    y0, x0, S = crop_box(frames.shape[1], frames.shape[2])
+    lut = norm_table()
+    out = [lut[resize_twin(np.ascontiguousarray(f[y0:y0 + S, x0:x0 + S]), R)] for f in frames]
+    return np.stack(out).transpose(3, 0, 1, 2)
+
+
+# ---- device side ---------------------------------------------------------------------------------------------------------
+_plans = {}
+
+
+class _Plan:
+    """everything the kernel needs for one (Hs, Ws, R), on one device"""
+
+    def __init__(self, Hs, Ws, R, device):
+        self.y0, self.x0, self.S = crop_box(Hs, Ws)
+        self.R = R
+        self.resize = self.S != R
+        if self.resize:
+            xmin, cnt, k = axis_coeffs(self.S, R)
+            self.K = k.shape[1]
+            tab = np.concatenate([xmin, cnt, k.reshape(-1)]).astype(np.int32)
+            # rows per workgroup: at most MAX_TILE_ROWS, and the source rows of the widest tile must fit the LDS
+            rows = MAX_TILE_ROWS
+            while True:
+                span = max(int(xmin[min(r + rows, R) - 1] + cnt[min(r + rows, R) - 1] - xmin[r]) for r in range(0, R, rows))
+                if span * R * 3 <= MAX_LDS_BYTES or rows == 1:
+                    break
+                rows //= 2
+            if span * R * 3 > MAX_LDS_BYTES:
+                raise ValueError(f"frame ingest: {Hs}x{Ws} -> {R} needs {span} source rows of {R * 3} B in LDS for one output row")
+            self.rows, self.span = rows, span
+        else:
+            self.K, self.rows, self.span = 0, 0, 0
+            tab = np.zeros(1, np.int32)
+        self.tab = torch.from_numpy(tab).to(device)
+        self.lut = torch.from_numpy(norm_table()).to(device)
+
+
+def plan(Hs, Ws, R, device):
+    key = (int(Hs), int(Ws), int(R), torch.device(device))
+    p = _plans.get(key)
+    if p is None:
+        p = _plans[key] = _Plan(Hs, Ws, R, device)
+    return p
+
+
+def frames_to_video(frames, R, out=None, slots=None):
+    """uint8 frames [B, T, Hs, Ws, 3] on the GPU -> the reference's float32 clip [B, 3, T, R, R].  With `out`
+    [Bout, 3, T, R, R] and `slots` (int32 [B] on the device), clip i is written to out[slots[i]] (mixed-size batches)."""
+    if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+        raise ValueError(f"frame ingest: expected uint8 [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_cuda:
+        raise ValueError("frame ingest runs on the GPU: move the frames to the device first")
+    frames = frames.contiguous()
+    B, T, Hs, Ws, _ = frames.shape
+    p = plan(Hs, Ws, R, frames.device)
+    if out is None:
+        if slots is not None:
+            raise ValueError("frame ingest: `slots` needs `out`")
+        out = torch.empty(B, 3, T, R, R, device=frames.device, dtype=torch.float32)
+    else:
+        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape[1:]) != (3, T, R, R):
+            raise ValueError(f"frame ingest: `out` must be contiguous float32 [*, 3, {T}, {R}, {R}], got {tuple(out.shape)}")
+        if slots is None and out.shape[0] != B:
+            raise ValueError("frame ingest: `out` has another batch size and no `slots` were given")
+    if slots is not None:
+        if slots.dtype != torch.int32 or slots.numel() != B or slots.device != frames.device:
+            raise ValueError("frame ingest: `slots` must be int32 [B] on the frames' device")
+    if B == 0:
+        return out
+    _lib.check(_lib.load().mebt_op_frames_to_video(
+        _lib.ptr(frames), _lib.ptr(out), B * T, T, Hs, Ws, p.y0, p.x0, p.S, R, _lib.ptr(p.tab), p.K, p.rows, p.span,
+        _lib.ptr(p.lut), _lib.ptr(slots), int(out.shape[0]), _lib.cur_stream()))
+    return out
+
+
+class RawVideoBatch:
+    """a collated batch of raw clips: `groups` = [(uint8 [b, T, Hs, Ws, 3], batch slots [b])], one group per source size, in
+    order of first appearance; `to_video()` runs the ingest once per group into one [B, 3, T, R, R] tensor."""
+
+    def __init__(self, groups, batch_size, resolution):
+        self.groups, self.batch_size, self.resolution = groups, int(batch_size), int(resolution)
+
+    @property
+    def shape(self):
+        T = self.groups[0][0].shape[1]
+        return (self.batch_size, 3, T, self.resolution, self.resolution)
+
+    def __len__(self):
+        return self.batch_size
+
+    def pin_memory(self):
+        return RawVideoBatch([(f.pin_memory(), s.pin_memory()) for f, s in self.groups], self.batch_size, self.resolution)
+
+    def to(self, device, non_blocking=False):
+        return RawVideoBatch([(f.to(device, non_blocking=non_blocking), s.to(device, non_blocking=non_blocking))
+                              for f, s in self.groups], self.batch_size, self.resolution)
+
+    def to_video(self):
+        f0 = self.groups[0][0]
+        if len(self.groups) == 1 and self.groups[0][1].numel() == self.batch_size:
+            return frames_to_video(f0, self.resolution)         # one size: the collate keeps batch order
+        out = torch.empty(self.shape, device=f0.device, dtype=torch.float32)
+        for f, s in self.groups:
+            frames_to_video(f, self.resolution, out=out, slots=s)
+        return out
+
+
+def collate_raw(items, resolution):
+    """collate for FrameListDataset(raw=True) items: clips that share a source size are stacked together (one ingest
+    launch per size); `indices` are stacked in batch order like the default collate"""
+    groups = {}
+    for i, it in enumerate(items):
+        v = it["video"]
+        groups.setdefault(tuple(v.shape), []).append(i)
+    out = []
+    for key, slots in groups.items():
+        out.append((torch.stack([items[i]["video"] for i in slots]), torch.tensor(slots, dtype=torch.int32)))
+    batch = {"video": RawVideoBatch(out, len(items), resolution)}
+    for k in items[0]:
+        if k != "video":
+            batch[k] = torch.utils.data.default_collate([it[k] for it in items])
+    return batch
+
+
+def to_device_video(x, device, non_blocking=True):
+    """a batch's `video` on the device, as the model consumes it: token grids and float clips are moved as they are, a raw
+    batch is moved as uint8 and run through the ingest kernel"""
+    if isinstance(x, RawVideoBatch):
+        return x.to(device, non_blocking=non_blocking).to_video()
+    return x.to(device, non_blocking=non_blocking)
+

@@ -10,7 +10,9 @@ Same config handling as the reference (YAML list + dot-list overrides, train_tra
 exp.{exact_lr,warmup_steps,weight_decay,cosine_lr}, :45-66), seed 42 on every rank (:11) so all ranks
 draw the same `t`; one process per GPU with RCCL all-reduce (DDP, :39-41).  Data: token grids from a
 `.npz` / `.h5` token file with the reference's `{train,test}_data` / `_idx` keys (`--tokens` or `data.data_path`,
-mebt_amd/data.py) or synthetic grids; every item carries `indices = randperm(T*H*W)` like the reference datasets
+mebt_amd/data.py), frame folders (the shipped YAMLs' `image_folder: True`: `[VIDEO_ID]_[FRAME_NUM].png` files listed in
+`data.data_path`/train.txt and test.txt, tokenized each step by the frozen 3D-VQGAN of `model.vqvae.params.ckpt_path`)
+or synthetic grids; every item carries `indices = randperm(T*H*W)` like the reference datasets
 (mebt/data.py:85,233,413,471); ranks read disjoint shards (DistributedSampler semantics).
 Checkpoints use the Lightning layout {'state_dict','hyper_parameters','global_step','epoch'} plus 'mebt_amd_loop'
 (AdamW moments, step counters, RNG states); `--ckpt_path` RESUMES from them (weights only when the file has no loop state).
@@ -58,6 +60,29 @@ def parse_gpus(spec, visible=None, device_count=None):
         except IndexError:
             raise ValueError(f"--gpus {spec} selects a device outside HIP_VISIBLE_DEVICES={visible}") from None
     return len(ids), ids
+
+
+def frame_folder_data(dcfg, tokens=None):
+    """True when the run trains from pixels (the reference's `image_folder` branch): the config's data node sets
+    image_folder and not vtokens, data_path is a directory holding train.txt, and no --tokens file overrides it."""
+    if tokens or not dcfg.get("image_folder", False) or dcfg.get("vtokens", False):
+        return False
+    path = dcfg.get("data_path", None)
+    return bool(path) and os.path.isdir(path) and os.path.isfile(os.path.join(path, "train.txt"))
+
+
+def check_first_stage(cfg):
+    """Frame-folder training tokenizes every batch with the frozen 3D-VQGAN: the model needs vtokens False and a first-stage
+    checkpoint (reference transformer.py:180-192).  Raises SystemExit with what to set."""
+    params, vq = cfg.model.params, cfg.model.get("vqvae", None)
+    ckpt = vq.get("params", {}).get("ckpt_path", None) if vq else None
+    if params.get("vtokens", False):
+        raise SystemExit("frame-folder data (data.image_folder: True) needs model.params.vtokens=False: the batches are pixels")
+    if not ckpt:
+        raise SystemExit("frame-folder data (data.image_folder: True) needs a 3D-VQGAN first stage to tokenize the frames: set "
+                         "model.vqvae.params.ckpt_path=<checkpoint>, or train from a token file with --tokens")
+    if not os.path.isfile(ckpt):
+        raise SystemExit(f"model.vqvae.params.ckpt_path={ckpt}: no such file")
 
 
 def main():
@@ -108,6 +133,11 @@ def main():
 
     cfg = getattr(presets, args.preset)() if args.preset else load_config(args.base, unknown)
     cfg.model.params.class_cond_dim = None
+    from .config import AttrDict
+    dargs = AttrDict(dict(cfg.data)) if "data" in cfg else AttrDict()
+    frames = frame_folder_data(dargs, args.tokens)
+    if frames:
+        check_first_stage(cfg)
     model = presets.build_model(cfg, compute_dtype=args.dtype)
     ckpt = None
     if args.ckpt_path:
@@ -125,19 +155,28 @@ def main():
     shape = list(cfg.model.mask.params.shape)
     # data: the reference's `vtokens` contract (mebt/data.py:236-305,330-414) — token clips from an .npz / .h5 file with
     # {train,test}_data / _idx, or synthetic grids; every item carries indices = randperm(T*H*W); ranks read disjoint shards
-    from .config import AttrDict
-    from .data import TokenData
-    dargs = AttrDict(dict(cfg.data)) if "data" in cfg else AttrDict()
-    if args.tokens:
-        dargs["data_path"] = args.tokens
-    # token files are in latent units: clip length / crop come from the mask grid (the config's data node of the shipped
-    # YAMLs is in pixel units, e.g. sequence_length 16 frames -> 4 latent frames), the file's own grid is its resolution
-    dargs["latent_shape"] = shape
-    dargs["sequence_length"] = shape[0] * int(dargs.get("sample_every_n_frames", 1))
-    dargs["resolution"] = None
-    dargs["spatial_length"] = shape[1]
-    dargs.setdefault("batch_size", 6)
-    data = TokenData(dargs, world_size=world, rank=rank)
+    from .data import TokenData, VideoData
+    from .frames import to_device_video
+    if frames:
+        # the `image_folder` contract (mebt/data.py:419-521): clip length, resolution and frame stride in pixel units as the
+        # YAML gives them; the workers decode to uint8, the GPU crops / resizes / normalises (frames.py), the first stage
+        # tokenizes inside TrainLoop.step.  latent_shape = the mask grid (train_transformer.py:29)
+        if model.first_stage_model is None:
+            raise SystemExit("frame-folder data needs the 3D-VQGAN first stage, and the model was built without one")
+        dargs["latent_shape"] = shape
+        dargs.setdefault("batch_size", 6)
+        data = VideoData(dargs, world_size=world, rank=rank, raw=True)
+    else:
+        if args.tokens:
+            dargs["data_path"] = args.tokens
+        # token files are in latent units: clip length / crop come from the mask grid (the config's data node of the shipped
+        # YAMLs is in pixel units, e.g. sequence_length 16 frames -> 4 latent frames), the file's own grid is its resolution
+        dargs["latent_shape"] = shape
+        dargs["sequence_length"] = shape[0] * int(dargs.get("sample_every_n_frames", 1))
+        dargs["resolution"] = None
+        dargs["spatial_length"] = shape[1]
+        dargs.setdefault("batch_size", 6)
+        data = TokenData(dargs, world_size=world, rank=rank)
     loader = data.train_dataloader()
     # `opt_step` counts OPTIMIZER steps (Lightning's global_step: --max_steps, the checkpointed 'global_step' and the LR /
     # beta(t) / t_prior schedules all count those); with accumulate_grad_batches = k a step is k micro-batches
@@ -159,7 +198,8 @@ def main():
         for bi, vb in enumerate(vl):
             if args.limit_val_batches and bi >= args.limit_val_batches:
                 break
-            vb = {k: (v.to(dev, non_blocking=True) if torch.is_tensor(v) else v) for k, v in vb.items()}
+            vb = {k: (to_device_video(v, dev) if k == "video" else v.to(dev, non_blocking=True) if torch.is_tensor(v) else v)
+                  for k, v in vb.items()}
             with torch.no_grad():
                 acc1, acc5, loss, _ = model.shared_step(vb, bi)
             tot += torch.stack([loss.double().reshape(()), torch.as_tensor(acc1, device=dev).double().reshape(()),

@@ -8,6 +8,7 @@ import random
 import numpy as np
 import torch
 
+from .frames import RawVideoBatch
 from .parallel import GradReducer, pick_concurrent_stream
 
 
@@ -67,9 +68,16 @@ class TrainLoop:
     def step(self, x, indices, t=None, flush=False):
         """x [B,T,H,W] int64 tokens, indices [B,N] permutations.  Returns a device tensor
         [CE sum, #top1, #top5, #rows, loss] (float64) — read it only when you want to log.
+        x may also be a pixel video [B,3,T,H,W] float (the reference's batch contract) or a raw uint8 batch from
+        frames.collate_raw (run through the GPU frame ingest first): both are tokenized by model.encode_to_z, then the
+        token step below runs unchanged.
         flush (gradient accumulation only): this is the last batch of the epoch — run the optimizer now even if the group
         is short, as Lightning does (its accumulation scheduler steps on `is_last_batch`; the loss stays divided by k)."""
         m, nm, red = self.model, self.native, self.reducer
+        if isinstance(x, RawVideoBatch):
+            x = x.to_video()
+        if x.dtype != torch.long:
+            x = m.encode_to_z(x)[1]                  # [B, t*h*w] token ids of the frozen first stage
         B = x.shape[0]
         x_ids = x.reshape(B, -1)
         if t is None:
