@@ -389,10 +389,14 @@ int mebt_debug_clock_probe(unsigned long long* out4, uint64_t ref_ticks_100mhz, 
 void mebt_debug_side_stream(mebt_model* m, int32_t on);
 /* experiment: run that second stream's work on a caller-owned stream instead (NULL: back to the internal one) */
 void mebt_debug_set_side_stream(mebt_model* m, mebt_stream_t stream);
-/* Benchmarking / tests only: force the bf16 GEMM block tile (bm, bn in {128, 64}); (0, 0) restores the heuristic. */
+/* Benchmarking / tests only: force the bf16 GEMM block tile: bm x bn one of 192x128, 128x128, 96x128, 128x64, 64x128, 96x64, 64x64 or
+ * 256x256 (any other tile makes the launch fail with MEBT_STATUS_EINVAL); (0, 0) restores the tuned / heuristic choice. */
 void mebt_debug_gemm_tile(int32_t bm, int32_t bn);
-/* Benchmarking / tests only: force the bf16 GEMM staging: 0 register-staged, 2 LDS-DMA 2 stages, 1 LDS-DMA
- * 3-stage ring; -1 restores the measured heuristic. */
+/* Benchmarking / tests only: force the bf16 GEMM variant (the low byte of a tune-table value): 0 register-staged, 2-5 LDS-DMA ring of
+ * that depth (1 = 3), 8 + r the software-pipelined loop (r = 2-4), 16 + r two pipelines per workgroup (r = 2, 3), 32 + r / 64 + r split-K
+ * in 2 / 4 fp32 slabs (r = 2, 3), with the 256 x 256 tile 9 the two staggered wave groups (anything else there: the 8-wave kernel).  A
+ * variant the product cannot run falls back to the LDS-DMA ring of the tile.  100 + code: the same without the C store of plain
+ * epilogues (199: the tuned / heuristic choice without it; experiments only).  -1 restores the tuned / heuristic choice. */
 void mebt_debug_gemm_variant(int32_t dma);
 /* Benchmarking only: a caller-owned device buffer (>= 496 MiB) the operator-level mebt_op_gemm may use as tuner /
  * split-K scratch (model-level entry points use their workspace); NULL removes it. */
@@ -410,8 +414,9 @@ void mebt_debug_attn_legacy(int32_t bits);
 /* Tests only: the block order of the MFMA attention grids.  For a 1-D grid of T = X * H * B workgroups (X row blocks, H heads), workgroup
  * t writes t to pos_to_id[(b * H + h) * X + x] for the (x, h, b) it takes; xcd = 1 the XCD-local order, 0 the linear one. */
 int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int32_t xcd, int32_t* pos_to_id, mebt_stream_t stream);
-/* Diagnostics (tools/wgrad_bench.py): every grouped weight-gradient launch uses this tile (128 or 64 each way) and LDS ring depth
- * (2-4) instead of the tuned / shipped choice; tbm = 0 switches the override off. */
+/* Diagnostics (tools/wgrad_bench.py): every grouped weight-gradient launch uses this tile (128x128, 128x64, 64x128 or 64x64 with ring
+ * 2-4; 256x128 with ring 2-3; a deeper ring is clamped) instead of the tuned / shipped choice, any other tile makes the launch fail with
+ * MEBT_STATUS_EINVAL; tbm = 0 switches the override off. */
 void mebt_debug_grouped_config(int32_t tbm, int32_t tbn, int32_t ring);
 /* Benchmarking only: LDS-DMA ring depth (2 or 3) of the grouped weight-gradient GEMM. */
 void mebt_debug_grouped_stages(int32_t n);

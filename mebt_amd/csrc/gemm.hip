@@ -1,6 +1,6 @@
-// Host side of the bf16 / f32 GEMM family: validation, in-situ autotuning, split-K scratch, and dispatch to the four
-// per-layout translation units (gemm_kk/kr/rr/rk.hip, which hold the bf16 kernel instantiations; the device code and
-// the design notes are in gemm_kernels.h).  The fp32 parity kernel and the split-K reduce kernel are instantiated here.
+// Host side of the bf16 / f32 GEMM family: validation, in-situ autotuning, split-K scratch, and dispatch through the kernel tables
+// (the bf16 tables are defined by the four per-layout translation units gemm_kk/kr/rr/rk.hip, which hold those instantiations; the
+// device code and the design notes are in gemm_kernels.h).  The fp32 parity kernels and the split-K reduce kernels are instantiated here.
 #include "gemm_kernels.h"
 #include <algorithm>
 #include <cstdio>
@@ -14,62 +14,23 @@
 #include <sys/file.h>
 #include <unistd.h>
 
-void mebt_gemm_cfg_kk(const GemmParams&, int, int, int, int, hipStream_t);
-void mebt_gemm_cfg_kr(const GemmParams&, int, int, int, int, hipStream_t);
-void mebt_gemm_cfg_rr(const GemmParams&, int, int, int, int, hipStream_t);
-void mebt_gemm_cfg_rk(const GemmParams&, int, int, int, int, hipStream_t);
-void mebt_gemm_ks2_kk(const GemmParams&, int, int, int, hipStream_t);
-void mebt_gemm_ks2_kr(const GemmParams&, int, int, int, hipStream_t);
-void mebt_gemm_ks2_rr(const GemmParams&, int, int, int, hipStream_t);
-void mebt_gemm_ks2_rk(const GemmParams&, int, int, int, hipStream_t);
-void mebt_gemm_w8_kk(const GemmParams&, int, hipStream_t);
-void mebt_gemm_w8_kr(const GemmParams&, int, hipStream_t);
-void mebt_gemm_w8_rr(const GemmParams&, int, hipStream_t);
-void mebt_gemm_w8_rk(const GemmParams&, int, hipStream_t);
-void mebt_gemm_pp_kk(const GemmParams&, hipStream_t);
-void mebt_gemm_pp_kr(const GemmParams&, hipStream_t);
-void mebt_gemm_pp_rr(const GemmParams&, hipStream_t);
-void mebt_gemm_pp_rk(const GemmParams&, hipStream_t);
-int mebt_gemm_attrs_kk(); int mebt_gemm_attrs_kr(); int mebt_gemm_attrs_rr(); int mebt_gemm_attrs_rk();
-void mebt_gemm_pair_kk(GemmPair&, int, int, int, hipStream_t);
-void mebt_gemm_pair_kr(GemmPair&, int, int, int, hipStream_t);
-void mebt_gemm_grouped(GroupedWgrad&, int, int, int, hipStream_t);
-
-
-static void launch_bf16_ks2(const GemmParams& p, int tbm, int tbn, int ring, hipStream_t stream) {
-    if (p.a_kc && p.b_kc) mebt_gemm_ks2_kk(p, tbm, tbn, ring, stream);
-    else if (p.a_kc && !p.b_kc) mebt_gemm_ks2_kr(p, tbm, tbn, ring, stream);
-    else if (!p.a_kc && !p.b_kc) mebt_gemm_ks2_rr(p, tbm, tbn, ring, stream);
-    else mebt_gemm_ks2_rk(p, tbm, tbn, ring, stream);
-}
-static void launch_pair_config(GemmPair& g, int tbm, int tbn, int staging, hipStream_t stream) {
-    if (g.p[0].b_kc) mebt_gemm_pair_kk(g, tbm, tbn, staging, stream);
-    else mebt_gemm_pair_kr(g, tbm, tbn, staging, stream);
-}
-static void launch_grouped_config(GroupedWgrad& c, int tbm, int tbn, int stages, hipStream_t stream) { mebt_gemm_grouped(c, tbm, tbn, stages, stream); }
-
-
 // ------------------------------------------------------------------------------------------------
 // host launcher
 // ------------------------------------------------------------------------------------------------
 static int g_gemm_force_split = 0;
-static int g_gemm_force_tile = 0;     // (BM << 12) | BN, tests / tools only
+static int g_gemm_force_tbm = 0, g_gemm_force_tbn = 0;     // tests / tools only
 static int g_grouped_stages = 2;
 extern "C" void mebt_debug_grouped_stages(int n) { g_grouped_stages = n; }
-static int g_grouped_force = 0;       // (tbm << 20) | (tbn << 8) | ring: tools/wgrad_bench.py times tile shapes the table does not hold
+static int g_grouped_force = 0;       // a packed GemmConfig: tools/wgrad_bench.py times tile shapes the table does not hold
 extern "C" void mebt_debug_grouped_config(int32_t tbm, int32_t tbn, int32_t ring) { g_grouped_force = (tbm && tbn) ? ((tbm << 20) | (tbn << 8) | ring) : 0; }
-static int g_gemm_dma = -1;           // -1 autotune / heuristic; forced (tests, tools): 0 register-staged, 2..5 LDS-DMA ring depth, 16+r two pipelines, 32+r / 64+r split-K 2 / 4
+static int g_gemm_dma = -1;           // -1 autotune / heuristic; forced (tests, tools): a GemmConfig code byte
 static int g_gemm_nostore = 0;        // experiments only (variant >= 100): skip the C store of plain epilogues
 extern "C" void mebt_debug_gemm_variant(int dma) { g_gemm_nostore = dma >= 100; g_gemm_dma = dma >= 100 ? (dma == 199 ? -1 : dma - 100) : dma; }
 void mebt_gemm_force_split(int s) { g_gemm_force_split = s; }
 static unsigned long long* g_gemm_stamps = nullptr;
 extern "C" void mebt_debug_gemm_stamps(unsigned long long* buf) { g_gemm_stamps = buf; }
-extern "C" void mebt_debug_gemm_tile(int bm, int bn) { g_gemm_force_tile = (bm && bn) ? ((bm << 12) | bn) : 0; }
+extern "C" void mebt_debug_gemm_tile(int bm, int bn) { g_gemm_force_tbm = (bm && bn) ? bm : 0; g_gemm_force_tbn = (bm && bn) ? bn : 0; }
 
-// one bf16 launch with an explicit (block tile, staging) choice; staging 0 = register-staged 2 stages,
-// 2..5 = LDS-DMA ring with that many stages (clamped to what the tile's LDS footprint admits)
-// scratch for split-K partials (library-owned, grown on demand; launches that use it are ordered on ONE stream: the
-// autotuner only offers split configurations for bf16-output products, i.e. the forward / dgrad chain)
 // Scratch of the tuner and of the split-K variant.  Caller-owned (the engine carves it out of the workspace PyTorch
 // allocated, `GemmParams::scratch`); operator-level callers without one get the heuristic configuration, or the
 // process-wide buffer a benchmark tool installed through mebt_debug_gemm_scratch().
@@ -95,44 +56,102 @@ extern "C" void mebt_debug_gemm_scratch(void* buf, int64_t bytes) {
     if (!buf || bytes < (int64_t)(MEBT_TUNE_FLUSH_BYTES + MEBT_TUNE_SPLITK_BYTES)) { g_default_scratch = {nullptr, 0, nullptr, 0}; return; }
     g_default_scratch = {buf, MEBT_TUNE_FLUSH_BYTES, (float*)((char*)buf + MEBT_TUNE_FLUSH_BYTES), (size_t)bytes - MEBT_TUNE_FLUSH_BYTES};
 }
-static void launch_bf16_config(const GemmParams& p, int tbm, int tbn, int staging, int split, hipStream_t stream) {
-    if (tbm == 256 && tbn == 256 && staging == 9 && p.a_kc && p.K % BK == 0) {   // two staggered wave groups (gemm_bf16_pp_kernel)
-        if (p.b_kc) mebt_gemm_pp_kk(p, stream); else mebt_gemm_pp_kr(p, stream);
-        return;
-    }
-    if (tbm == 256 && tbn == 256) {   // the 8-wave tile: whole reduction in the workgroup, ring 2
-        if (p.a_kc && p.b_kc) mebt_gemm_w8_kk(p, 2, stream);
-        else if (p.a_kc && !p.b_kc) mebt_gemm_w8_kr(p, 2, stream);
-        else if (!p.a_kc && !p.b_kc) mebt_gemm_w8_rr(p, 2, stream);
-        else mebt_gemm_w8_rk(p, 2, stream);
-        return;
-    }
-    if (staging >= 16) {          // two pipelines: whole reduction in the workgroup, an even number of k-tiles
-        if (split == 1 && p.K % (2 * BK) == 0 && ks2_lds(tbm, tbn, staging - 16)) { launch_bf16_ks2(p, tbm, tbn, staging - 16, stream); return; }
-        staging -= 16;
-    }
-    if (p.a_kc && p.b_kc) mebt_gemm_cfg_kk(p, tbm, tbn, staging, split, stream);
-    else if (p.a_kc && !p.b_kc) mebt_gemm_cfg_kr(p, tbm, tbn, staging, split, stream);
-    else if (!p.a_kc && !p.b_kc) mebt_gemm_cfg_rr(p, tbm, tbn, staging, split, stream);
-    else mebt_gemm_cfg_rk(p, tbm, tbn, staging, split, stream);
-}
 static bool splitk_fits(const GemmParams& p, int S) {
     const GemmScratch* sc = scratch_of(p.scratch);
     return sc && sc->splitk && (size_t)S * p.M * p.N * 4 <= sc->splitk_bytes;
 }
-static int launch_bf16_splitk(const GemmParams& p, int tbm, int tbn, int ring, int S, hipStream_t stream) {
-    const GemmScratch* sc = scratch_of(p.scratch);
-    if (!splitk_fits(p, S)) { mebt_set_error("gemm: split-K scratch missing or too small"); return MEBT_EWORKSPACE; }
-    float* g_sk_buf = sc->splitk;
+
+// ------------------------------------------------------------------------------------------------
+// kernel tables and resolvers
+// ------------------------------------------------------------------------------------------------
+static const GemmTables& tables_of(bool a_kc, bool b_kc) {
+    static const GemmTables t[4] = {mebt_gemm_tables_rr(), mebt_gemm_tables_rk(), mebt_gemm_tables_kr(), mebt_gemm_tables_kk()};
+    return t[a_kc * 2 + b_kc];
+}
+#define F32(AK, BKC, TM, TN) {GemmVariant::reg, TM, TN, 0, 256, 0, (const void*)&gemm_f32_kernel<AK, BKC, TM, TN>}
+#define F32_TILES(AK, BKC) {F32(AK, BKC, 128, 128), F32(AK, BKC, 128, 64), F32(AK, BKC, 64, 128), F32(AK, BKC, 64, 64)}
+static const GemmKernel f32_kernels[4][4] = {F32_TILES(false, false), F32_TILES(false, true), F32_TILES(true, false), F32_TILES(true, true)};
+#undef F32_TILES
+#undef F32
+static const GemmKernel splitk_reduce[2] = {{GemmVariant::splitk2, 0, 0, 0, 256, 0, (const void*)&splitk_reduce_kernel<2>},
+                                            {GemmVariant::splitk4, 0, 0, 0, 256, 0, (const void*)&splitk_reduce_kernel<4>}};
+
+// The entry of `t` for variant v and tile tbm x tbn with the deepest ring <= `ring` (the shallowest one when every ring is deeper);
+// null when the table has no such tile.  Entries that need more LDS than a CU has are never chosen.
+static const GemmKernel* gemm_find(const GemmTable& t, GemmVariant v, int tbm, int tbn, int ring) {
+    const GemmKernel* best = nullptr;
+    for (int i = 0; i < t.n; ++i) {
+        const GemmKernel& k = t.k[i];
+        if (k.v != v || k.tbm != tbm || k.tbn != tbn || k.lds > kMaxLds) continue;
+        const bool fits = k.ring <= ring, best_fits = best && best->ring <= ring;
+        if (!best || (fits && (!best_fits || k.ring > best->ring)) || (!fits && !best_fits && k.ring < best->ring)) best = &k;
+    }
+    return best;
+}
+static const GemmKernel* gemm_find_exact(const GemmTable& t, GemmVariant v, int tbm, int tbn, int ring) {
+    const GemmKernel* k = gemm_find(t, v, tbm, tbn, ring);
+    return k && k->ring == ring ? k : nullptr;
+}
+static int no_kernel(const char* family, const GemmConfig& c) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: no kernel for a %d x %d block tile", family, c.tbm, c.tbn);
+    mebt_set_error(msg);
+    return MEBT_EINVAL;
+}
+static int launch_kernel(const GemmKernel& k, dim3 grid, void** args, hipStream_t stream) {
+    MEBT_HIP_CHECK(hipLaunchKernel(k.fn, grid, dim3(k.threads), args, k.lds, stream));
+    return MEBT_OK;
+}
+
+// What runs for configuration c on product p (split: ways of the atomic split-K, 1 = none): the kernel, and S > 1 when it writes S
+// fp32 slabs that splitk_reduce_kernel adds up.  A variant this product cannot run falls back to the LDS-DMA ring of its tile, as deep as
+// the tile has; a tile without kernels is MEBT_EINVAL.
+static int resolve_bf16(const GemmParams& p, GemmConfig c, int split, const GemmKernel*& k, int& S) {
+    typedef GemmVariant V;
+    const GemmTable& t = tables_of(p.a_kc, p.b_kc).single;
+    S = 1;
+    if (c.v == V::dma && c.ring == 1) c.ring = 3;
+    if (c.tbm == 256 && c.tbn == 256) {          // the staggered groups need A KC and whole k-tiles; otherwise the 8-wave kernel, ring 2
+        const bool pp = c.v == V::pp && p.a_kc && p.K % BK == 0;
+        c.v = pp ? V::pp : V::w8;
+        c.ring = pp ? 0 : 2;
+    }
+    if (c.v == V::splitk2 || c.v == V::splitk4) {
+        const int s = c.v == V::splitk2 ? 2 : 4;
+        if (!p.c_f32 && p.C && split == 1 && p.K % (s * BK) == 0 && !p.beta && splitk_fits(p, s)) S = s;
+        c.v = V::dma;
+    }
+    k = nullptr;
+    if (c.v == V::ks2 && split == 1 && p.K % (2 * BK) == 0) k = gemm_find_exact(t, V::ks2, c.tbm, c.tbn, c.ring);   // an even number of k-tiles
+    else if (c.v == V::pipe && split == 1 && !p.slab) k = gemm_find_exact(t, V::pipe, c.tbm, c.tbn, c.ring);
+    else if (c.v == V::reg || c.v == V::w8 || c.v == V::pp) k = gemm_find_exact(t, c.v, c.tbm, c.tbn, c.ring);
+    if (!k) k = gemm_find(t, V::dma, c.tbm, c.tbn, c.ring);
+    return k ? MEBT_OK : no_kernel("gemm", c);
+}
+static int launch_single(const GemmParams& p, const GemmKernel& k, int split, hipStream_t stream) {
+    dim3 grid((p.N + k.tbn - 1) / k.tbn, (p.M + k.tbm - 1) / k.tbm, k.v == GemmVariant::dma || k.v == GemmVariant::reg ? split : 1);
+    if (k.v == GemmVariant::pp) grid = dim3(std::min(grid.x * grid.y, 256u));      // persistent over the tile list: one workgroup per CU
+    void* args[] = {const_cast<GemmParams*>(&p)};
+    return launch_kernel(k, grid, args, stream);
+}
+// split-K into S fp32 slabs of the scratch (resolve_bf16 checked that they fit), then the reduce kernel applies the real epilogue
+static int launch_splitk(const GemmParams& p, const GemmKernel& k, int S, hipStream_t stream) {
     GemmParams q = p;
-    q.C = g_sk_buf; q.C2 = nullptr; q.c_f32 = 1; q.ldc = p.N; q.epilogue = EPI_NONE; q.bias = nullptr; q.aux = nullptr; q.beta = 0;
+    float* part = scratch_of(p.scratch)->splitk;
+    q.C = part; q.C2 = nullptr; q.c_f32 = 1; q.ldc = p.N; q.epilogue = EPI_NONE; q.bias = nullptr; q.aux = nullptr; q.beta = 0;
     q.drop.thresh = 0; q.slab = (long)p.M * p.N;
-    launch_bf16_config(q, tbm, tbn, ring, S, stream);
+    if (int rc = launch_single(q, k, S, stream)) return rc;
     const long total = (long)p.M * (p.N / 4);
     const unsigned blocks = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (S == 2) hipLaunchKernelGGL(splitk_reduce_kernel<2>, dim3(blocks), dim3(256), 0, stream, p, g_sk_buf, q.slab);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<4>, dim3(blocks), dim3(256), 0, stream, p, g_sk_buf, q.slab);
-    return MEBT_OK;
+    long slab = q.slab;
+    void* args[] = {const_cast<GemmParams*>(&p), &part, &slab};
+    return launch_kernel(splitk_reduce[S == 4], dim3(blocks), args, stream);
+}
+static int launch_config(const GemmParams& p, const GemmConfig& c, int split, hipStream_t stream) {
+    const GemmKernel* k;
+    int S;
+    if (int rc = resolve_bf16(p, c, split, k, S)) return rc;
+    return S > 1 ? launch_splitk(p, *k, S, stream) : launch_single(p, *k, split, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -161,12 +180,13 @@ static int tune_bucket_m(const GemmParams& p) {          // GemmParams::coarse_m
     while (b < p.M) b <<= 1;
     return b;
 }
-static std::map<TuneKey, int> g_tuned;      // -> (tbm << 20) | (tbn << 8) | staging
+static std::map<TuneKey, int> g_tuned;      // -> GemmConfig::encode() (pair: 0 = two separate launches)
+struct TuneCand { int code; float ms; };    // a packed GemmConfig and its cold time
 // the fastest few candidates of every signature tuned in this process, with their isolated (cold) times: what tools/step_tune.py
 // tries one by one IN the train step (a candidate that is second in isolation can be first between its real neighbours)
-static std::map<TuneKey, std::vector<std::pair<int, float>>> g_alts;
-static void alts_keep(const TuneKey& key, std::vector<std::pair<int, float>> v) {
-    std::sort(v.begin(), v.end(), [](const std::pair<int, float>& a, const std::pair<int, float>& b) { return a.second < b.second; });
+static std::map<TuneKey, std::vector<TuneCand>> g_alts;
+static void alts_keep(const TuneKey& key, std::vector<TuneCand> v) {
+    std::sort(v.begin(), v.end(), [](const TuneCand& a, const TuneCand& b) { return a.ms < b.ms; });
     if (v.size() > 4) v.resize(4);
     g_alts[key] = v;
 }
@@ -199,7 +219,7 @@ static int tune_parse(const char* text, bool overwrite, bool replace = false) {
         int v;
         if (!ok || !next_int(v)) break;
         if (n == 1 && k[0] == -1) version = v;
-        else ent.emplace_back(k, v);
+        else ent.emplace_back(k, GemmConfig::decode(v).encode());      // the packing round-trips: what is read is what is exported
     }
     if (version != MEBT_TUNE_VERSION) return 0;
     if (replace) g_tuned.clear();
@@ -315,7 +335,7 @@ extern "C" int64_t mebt_gemm_tune_alternatives(char* buf, int64_t cap) {
         text += std::to_string(e.first.size());
         for (int x : e.first) { text += ' '; text += std::to_string(x); }
         text += " :";
-        for (auto& a : e.second) { snprintf(tmp, sizeof tmp, " %d %.2f", a.first, a.second * 1e3f); text += tmp; }
+        for (auto& a : e.second) { snprintf(tmp, sizeof tmp, " %d %.2f", a.code, a.ms * 1e3f); text += tmp; }
         text += '\n';
     }
     const int64_t need = (int64_t)text.size() + 1;
@@ -366,7 +386,7 @@ template <typename F>
 static int time_cold(F&& launch, hipStream_t stream, const TuneRun& tr, float& best_ms) {
     float tot = 0.f;
     hipEvent_t e0 = tr.e0, e1 = tr.e1;
-    launch();                                                                    // code object, TLBs
+    if (int rc = launch()) return rc;                                            // code object, TLBs
     static const int warm = [] { const char* e = getenv("MEBT_GEMM_TUNE_WARM"); return e ? atoi(e) : 0; }();   // experiment: time candidates on warm caches
     // How cold?  In the step a product's weights were prefetched into the Infinity Cache by its predecessor and its activations
     // were just written: L2-cold, Infinity-Cache-warm.  A 384 MB flush also empties the 256 MB Infinity Cache and ranks the
@@ -377,7 +397,7 @@ static int time_cold(F&& launch, hipStream_t stream, const TuneRun& tr, float& b
     for (int r = 0; r < 2; ++r) {
         if (!warm) MEBT_HIP_CHECK(hipMemsetAsync(tr.sc->flush, r, tr.sc->flush_bytes < flush_cap ? tr.sc->flush_bytes : flush_cap, stream));
         MEBT_HIP_CHECK(hipEventRecord(e0, stream));
-        launch();
+        if (int rc = launch()) return rc;
         MEBT_HIP_CHECK(hipEventRecord(e1, stream));
         MEBT_HIP_CHECK(hipEventSynchronize(e1));
         float ms = 0.f;
@@ -388,102 +408,98 @@ static int time_cold(F&& launch, hipStream_t stream, const TuneRun& tr, float& b
     return MEBT_OK;
 }
 
-static int autotune_config(const GemmParams& p, hipStream_t stream, int& tbm, int& tbn, int& staging, std::vector<std::pair<int, float>>* alts = nullptr) {
+// a packed configuration as the tuner's log lines show it
+static std::string describe(int code) {
+    static const char* const what[] = {"", " register-staged", " pipelined", " x2 pipelines", " (8 waves)", " (2 x 4 waves, staggered, persistent)", " split-K 2", " split-K 4"};
+    const GemmConfig c = GemmConfig::decode(code);
+    char b[96];
+    snprintf(b, sizeof b, "%dx%d ring %d%s", c.tbm, c.tbn, c.ring, what[(int)c.v]);
+    return b;
+}
+// The tuners' shared steps.  tune_sweep times every candidate once, in the tuner's order, and logs it (MEBT_GEMM_TUNE_LOG=2); `best` is
+// the index of the fastest, the first of equal times (so the candidate order is part of the outcome), -1 for none.
+template <typename F>
+static int tune_sweep(std::vector<TuneCand>& cands, F&& launch, hipStream_t stream, const TuneRun& tr, const char* what, int& best) {
+    best = -1;
+    for (size_t i = 0; i < cands.size(); ++i) {
+        const int code = cands[i].code;
+        if (int rc = time_cold([&] { return launch(code); }, stream, tr, cands[i].ms)) return rc;
+        if (g_tune_log >= 2) fprintf(stderr, "    cand %s%s: %.1f us\n", what, describe(code).c_str(), cands[i].ms * 1e3f);
+        if (best < 0 || cands[i].ms < cands[best].ms) best = (int)i;
+    }
+    return MEBT_OK;
+}
+// tune_record keeps the fastest alternatives, enters the choice and appends it to MEBT_GEMM_TUNE_CACHE (under g_tune_mutex)
+static std::map<TuneKey, int>::iterator tune_record(const TuneKey& key, const std::vector<TuneCand>& alts, int choice) {
+    alts_keep(key, alts);
+    auto it = g_tuned.emplace(key, choice).first;
+    tune_remember(key, it->second);
+    return it;
+}
+
+// The single-product tuner: every (tile, variant, ring) this product can use, timed once, then the four fastest three more times
+// (under g_tune_mutex).
+static int autotune_single(const GemmParams& p, const TuneKey& key, hipStream_t stream) {
+    typedef GemmVariant V;
     TuneRun tr;
     if (int rc = tr.begin(scratch_of(p.scratch))) return rc;
-    static const int tiles[7][2] = {{192, 128}, {128, 128}, {96, 128}, {128, 64}, {64, 128}, {96, 64}, {64, 64}};
+    const GemmTable& t = tables_of(p.a_kc, p.b_kc).single;
+    std::vector<std::pair<int, int>> tiles;                   // the LDS-DMA tiles in table order
+    for (int i = 0; i < t.n; ++i)
+        if (t.k[i].v == V::dma && std::find(tiles.begin(), tiles.end(), std::make_pair(t.k[i].tbm, t.k[i].tbn)) == tiles.end()) tiles.emplace_back(t.k[i].tbm, t.k[i].tbn);
+    std::vector<TuneCand> cands;
+    auto offer = [&](int bm, int bn, int ring, V v, V table_v) {
+        if (gemm_find_exact(t, table_v, bm, bn, ring)) cands.push_back({GemmConfig{bm, bn, ring, v}.encode(), 0.f});
+    };
     const long out = (long)p.M * p.N;
-    float best = 1e30f;
-    struct Cand { float ms; int bm, bn, staging; };
-    std::vector<Cand> cands;
-    for (int t = 0; t < 7; ++t) {
-        const int bm = tiles[t][0], bn = tiles[t][1];
+    for (const auto& tile : tiles) {
+        const int bm = tile.first, bn = tile.second;
         const long nt = (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn);
         const bool few = nt < 96 && (long)bm * bn > 64 * 64 && out > 64 * 64;    // unsplit, this tile would leave most of the chip idle
-        for (int st = 2; st <= 4 && !few; ++st) {
-            if (st * (bm + bn) * BK * 2 > 128 * 1024) continue;
-            float ms = 0.f;
-            if (int rc = time_cold([&] { launch_bf16_config(p, bm, bn, st, 1, stream); }, stream, tr, ms)) return rc;
-            if (g_tune_log >= 2) fprintf(stderr, "    cand %dx%d ring %d: %.1f us\n", bm, bn, st, ms * 1e3f);
-            cands.push_back({ms, bm, bn, st});
-            if (ms < best) { best = ms; tbm = bm; tbn = bn; staging = st; }
-        }
-        for (int st = 2; st <= 4 && !few; ++st) {                                 // software-pipelined main loop (staging 8 + ring depth)
-            if (st * (bm + bn) * BK * 2 > 160 * 1024) continue;
-            float ms = 0.f;
-            if (int rc = time_cold([&] { launch_bf16_config(p, bm, bn, 8 + st, 1, stream); }, stream, tr, ms)) return rc;
-            if (g_tune_log >= 2) fprintf(stderr, "    cand %dx%d ring %d pipelined: %.1f us\n", bm, bn, st, ms * 1e3f);
-            cands.push_back({ms, bm, bn, 8 + st});
-            if (ms < best) { best = ms; tbm = bm; tbn = bn; staging = 8 + st; }
-        }
-        if (!p.c_f32 && p.C && nt <= 256 && (long)bm * bn >= 128 * 128)          // split-K into fp32 slabs + reduce/epilogue kernel (staging 32 * log2(S) + ring)
-            for (int S = 2; S <= 4; S *= 2) {
-                if (p.K % (S * BK) || p.K / S < 8 * BK || !splitk_fits(p, S)) continue;
-                for (int st = 2; st <= 3; ++st) {
-                    if (st * (bm + bn) * BK * 2 > 128 * 1024) continue;
-                    float ms = 0.f;
-                    int rc2 = MEBT_OK;
-                    if (int rc = time_cold([&] { rc2 |= launch_bf16_splitk(p, bm, bn, st, S, stream); }, stream, tr, ms)) return rc;
-                    if (rc2) return rc2;
-                    if (g_tune_log >= 2) fprintf(stderr, "    cand %dx%d ring %d split-K %d: %.1f us\n", bm, bn, st, S, ms * 1e3f);
-                    cands.push_back({ms, bm, bn, (S == 2 ? 32 : 64) + st});
-                    if (ms < best) { best = ms; tbm = bm; tbn = bn; staging = (S == 2 ? 32 : 64) + st; }
-                }
-            }
-        if (p.K % (2 * BK) == 0 && p.K >= 8 * BK && nt <= 640 && !few)         // two pipelines per workgroup (staging 16 + ring depth)
-            for (int st = 2; st <= 3; ++st) {
-                if (!ks2_lds(bm, bn, st)) continue;
-                float ms = 0.f;
-                if (int rc = time_cold([&] { launch_bf16_config(p, bm, bn, 16 + st, 1, stream); }, stream, tr, ms)) return rc;
-                if (g_tune_log >= 2) fprintf(stderr, "    cand %dx%d ring %d x2 pipelines: %.1f us\n", bm, bn, st, ms * 1e3f);
-                cands.push_back({ms, bm, bn, 16 + st});
-                if (ms < best) { best = ms; tbm = bm; tbn = bn; staging = 16 + st; }
-            }
+        for (int st = 2; st <= 4 && !few; ++st) offer(bm, bn, st, V::dma, V::dma);
+        for (int st = 2; st <= 4 && !few; ++st) offer(bm, bn, st, V::pipe, V::pipe);
+        if (!p.c_f32 && p.C && nt <= 256 && (long)bm * bn >= 128 * 128)          // split-K into fp32 slabs + reduce/epilogue kernel
+            for (int S = 2; S <= 4; S *= 2)
+                for (int st = 2; st <= 3 && p.K % (S * BK) == 0 && p.K / S >= 8 * BK && splitk_fits(p, S); ++st)
+                    offer(bm, bn, st, S == 2 ? V::splitk2 : V::splitk4, V::dma);
+        if (p.K % (2 * BK) == 0 && p.K >= 8 * BK && nt <= 640 && !few)         // two pipelines per workgroup
+            for (int st = 2; st <= 3; ++st) offer(bm, bn, st, V::ks2, V::ks2);
     }
     if ((long)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 96 && (p.a_kc ? p.K % BK == 0 : true)) {   // 8-wave 256 x 256 tile
-        float ms = 0.f;
-        if (int rc = time_cold([&] { launch_bf16_config(p, 256, 256, 2, 1, stream); }, stream, tr, ms)) return rc;
-        if (g_tune_log >= 2) fprintf(stderr, "    cand 256x256 (8 waves): %.1f us\n", ms * 1e3f);
-        cands.push_back({ms, 256, 256, 2});
-        if (ms < best) { best = ms; tbm = 256; tbn = 256; staging = 2; }
-        if (p.a_kc && p.K % BK == 0) {                     // the same tile as two staggered wave groups (staging code 9)
-            if (int rc = time_cold([&] { launch_bf16_config(p, 256, 256, 9, 1, stream); }, stream, tr, ms)) return rc;
-            if (g_tune_log >= 2) fprintf(stderr, "    cand 256x256 (2 x 4 waves, staggered): %.1f us\n", ms * 1e3f);
-            cands.push_back({ms, 256, 256, 9});
-            if (ms < best) { best = ms; tbm = 256; tbn = 256; staging = 9; }
-        }
+        offer(256, 256, 2, V::w8, V::w8);
+        if (p.a_kc && p.K % BK == 0) offer(256, 256, 0, V::pp, V::pp);          // the same tile as two staggered wave groups
     }
+    auto launch = [&](int code) { return launch_config(p, GemmConfig::decode(code), 1, stream); };
+    int best;
+    if (int rc = tune_sweep(cands, launch, stream, tr, "", best)) return rc;
+    int tbm, tbn, staging;
+    heuristic_config(p, tbm, tbn, staging);
+    int choice = best >= 0 ? cands[best].code : (tbm << 20) | (tbn << 8) | staging;
+    float best_ms = best >= 0 ? cands[best].ms : 1e30f;
     // Second round.  The sweep's minimum over ~40 two-sample means is biased towards a lucky sample (run-to-run the choice moved
     // between neighbours and the step time with it, +-0.1 ms at config 2): the four fastest are timed again, three more cold pairs
     // each, and the best mean of all eight samples wins.
-    std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.ms < b.ms; });
+    std::sort(cands.begin(), cands.end(), [](const TuneCand& a, const TuneCand& b) { return a.ms < b.ms; });
     const int finalists = (int)std::min<size_t>(4, cands.size());
     if (finalists > 1) {
-        best = 1e30f;
+        best_ms = 1e30f;
         for (int c = 0; c < finalists; ++c) {
-            Cand& k = cands[c];
+            TuneCand& k = cands[c];
             float sum = k.ms;
             for (int r = 0; r < 3; ++r) {
                 float ms = 0.f;
-                int rc2 = MEBT_OK;
-                if (int rc = time_cold([&] {
-                        if (k.staging >= 32 && k.bm != 256) rc2 |= launch_bf16_splitk(p, k.bm, k.bn, k.staging & 15, k.staging >= 64 ? 4 : 2, stream);
-                        else launch_bf16_config(p, k.bm, k.bn, k.staging, 1, stream);
-                    }, stream, tr, ms)) return rc;
-                if (rc2) return rc2;
+                if (int rc = time_cold([&] { return launch(k.code); }, stream, tr, ms)) return rc;
                 sum += ms;
             }
             k.ms = sum / 4;
-            if (g_tune_log >= 2) fprintf(stderr, "    finalist %dx%d code %d: %.1f us (mean of 8)\n", k.bm, k.bn, k.staging, k.ms * 1e3f);
-            if (k.ms < best) { best = k.ms; tbm = k.bm; tbn = k.bn; staging = k.staging; }
+            if (g_tune_log >= 2) fprintf(stderr, "    finalist %s: %.1f us (mean of 8)\n", describe(k.code).c_str(), k.ms * 1e3f);
+            if (k.ms < best_ms) { best_ms = k.ms; choice = k.code; }
         }
     }
-    if (alts)
-        for (int c = 0; c < finalists; ++c) alts->emplace_back((cands[c].bm << 20) | (cands[c].bn << 8) | cands[c].staging, cands[c].ms);
     if (g_tune_log)
-        fprintf(stderr, "[mebt gemm autotune] M=%d N=%d K=%d a_kc=%d b_kc=%d epi=%d c_f32=%d -> %dx%d ring %d%s (%.1f us cold)\n", p.M, p.N, p.K,
-                p.a_kc, p.b_kc, p.epilogue, p.c_f32, tbm, tbn, (tbm == 256 && staging == 9) ? 2 : (staging >= 8 && staging < 16) ? staging - 8 : (staging & 15),
-                (tbm == 256 && staging == 9) ? " two staggered groups, persistent" : staging >= 64 ? " split-K 4" : staging >= 32 ? " split-K 2" : staging >= 16 ? " x2 pipelines" : staging >= 8 ? " pipelined" : "", best * 1e3f);
+        fprintf(stderr, "[mebt gemm autotune] M=%d N=%d K=%d a_kc=%d b_kc=%d epi=%d c_f32=%d -> %s (%.1f us cold)\n", p.M, p.N, p.K,
+                p.a_kc, p.b_kc, p.epilogue, p.c_f32, describe(choice).c_str(), best_ms * 1e3f);
+    tune_record(key, std::vector<TuneCand>(cands.begin(), cands.begin() + finalists), choice);
     return MEBT_OK;
 }
 
@@ -511,18 +527,16 @@ int launch_gemm(const GemmParams& p_in, int dtype, hipStream_t stream) {
         split = max(1, min(p.split_k, nkt));
     }
     if (g_gemm_force_split > 0 && p.c_f32 && p.epilogue == EPI_NONE) split = g_gemm_force_split;
-    if (split > 1 && !p.beta) {
-        // split-K accumulates with fp32 atomics into a zeroed C
-        MEBT_HIP_CHECK(hipMemset2DAsync(p.C, (size_t)p.ldc * 4, 0, (size_t)p.N * 4, p.M, stream));
-    }
+    const GemmKernel* k = nullptr;
+    int S = 1;
     if (dtype == MEBT_BF16) {
-        int tbm = 128, tbn = 128, staging = 2;
-        const bool forced = g_gemm_force_tile || g_gemm_dma >= 0;
+        GemmConfig c;
+        bool have = false;
+        const bool forced = g_gemm_force_tbm || g_gemm_dma >= 0;
         // only launches that can be repeated are timed: no accumulation into C, no output aliasing the aux operand (an in-place
         // residual).  C = null (the inference form of the GELU product: only gelu(C) is stored) is repeatable — comparing it with a
         // null aux made every inference fc1 skip the tuner and run the heuristic tile (round 5: 427 -> 270 us at 32 768 rows)
         const bool idempotent = !p.beta && split == 1 && (p.C == nullptr || p.C != p.aux);
-        bool have = false;
         if (!forced && split == 1 && (long)p.M * p.N >= 128 * 128) {
             std::lock_guard<std::mutex> lk(g_tune_mutex);
             tune_init();
@@ -531,31 +545,22 @@ int launch_gemm(const GemmParams& p_in, int dtype, hipStream_t stream) {
                               tune_bucket_m(p), p.N, tune_bucket(p.K)};
             auto it = g_tuned.find(key);
             if (it == g_tuned.end() && g_autotune && idempotent && tune_scratch_of(p.scratch)) {
-                heuristic_config(p, tbm, tbn, staging);
-                std::vector<std::pair<int, float>> alts;
-                if (int rc = autotune_config(p, stream, tbm, tbn, staging, &alts)) return rc;
-                alts_keep(key, alts);
-                it = g_tuned.emplace(key, (tbm << 20) | (tbn << 8) | staging).first;
-                tune_remember(key, it->second);
+                if (int rc = autotune_single(p, key, stream)) return rc;
+                it = g_tuned.find(key);
             }
             if (it != g_tuned.end()) {
-                tbm = it->second >> 20; tbn = (it->second >> 8) & 0xFFF; staging = it->second & 255;
-                have = true;
-                if ((staging >= 16 && staging < 32 && p.K % (2 * BK)) || (tbm == 256 && p.a_kc && p.K % BK)) have = false;   // a bucket neighbour's variant that this K cannot run
+                c = GemmConfig::decode(it->second);
+                have = !(c.v == GemmVariant::ks2 && p.K % (2 * BK));       // a bucket neighbour's two-pipeline choice that this K cannot run
             }
         }
-        if (!have) {
+        if (!have) {                                                       // the heuristic, or what tests / tools force
+            int tbm, tbn, staging;
             heuristic_config(p, tbm, tbn, staging);
-            if (g_gemm_force_tile) { tbm = g_gemm_force_tile >> 12; tbn = g_gemm_force_tile & 0xFFF; }
-            if (g_gemm_dma >= 0) staging = g_gemm_dma == 1 ? 3 : g_gemm_dma;       // forced: 0 reg, 2..5 LDS-DMA stages (1 = 3)
+            if (g_gemm_force_tbm) { tbm = g_gemm_force_tbm; tbn = g_gemm_force_tbn; }
+            if (g_gemm_dma >= 0) staging = g_gemm_dma;
+            c = GemmConfig::decode((tbm << 20) | (tbn << 8) | staging);
         }
-        if (staging >= 32) {
-            const int S = staging >= 64 ? 4 : 2;
-            if (!p.c_f32 && p.C && split == 1 && p.K % (S * BK) == 0 && !p.beta && splitk_fits(p, S)) { if (int rc = launch_bf16_splitk(p, tbm, tbn, staging & 15, S, stream)) return rc; }
-            else launch_bf16_config(p, tbm, tbn, staging & 15, split, stream);
-        } else {
-            launch_bf16_config(p, tbm, tbn, staging, split, stream);
-        }
+        if (int rc = resolve_bf16(p, c, split, k, S)) return rc;
     } else if (dtype == MEBT_F32) {
         // the largest tile whose grid still fills the chip (256 CUs): 128 x 128, then the longer side halved, then 64 x 64
         // (MEBT_F32_TILE=128 keeps 128 x 128 everywhere: A/B of round 6)
@@ -566,40 +571,42 @@ int launch_gemm(const GemmParams& p_in, int dtype, hipStream_t stream) {
             if (p.M >= p.N) { tbm = 64; tbn = 128; } else { tbm = 128; tbn = 64; }
             if (wgs(tbm, tbn) < 256) { tbm = 64; tbn = 64; }
         }
-        dim3 grid((p.N + tbn - 1) / tbn, (p.M + tbm - 1) / tbm, split);
-#define LAUNCH_F32_T(AK, BKC)                                                                                                 \
-        do {                                                                                                                      \
-            if (tbm == 128 && tbn == 128) hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC, 128, 128>), grid, dim3(256), 0, stream, p);   \
-            else if (tbm == 128) hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC, 128, 64>), grid, dim3(256), 0, stream, p);          \
-            else if (tbn == 128) hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC, 64, 128>), grid, dim3(256), 0, stream, p);          \
-            else hipLaunchKernelGGL((gemm_f32_kernel<AK, BKC, 64, 64>), grid, dim3(256), 0, stream, p);                          \
-        } while (0)
-#define LAUNCH_F32(AK, BKC) LAUNCH_F32_T(AK, BKC)
-        if (p.a_kc && p.b_kc) LAUNCH_F32(true, true);
-        else if (p.a_kc && !p.b_kc) LAUNCH_F32(true, false);
-        else if (!p.a_kc && !p.b_kc) LAUNCH_F32(false, false);
-        else LAUNCH_F32(false, true);
-#undef LAUNCH_F32_T
-#undef LAUNCH_F32
+        k = gemm_find({f32_kernels[p.a_kc * 2 + p.b_kc], 4}, GemmVariant::reg, tbm, tbn, 0);
     } else {
         mebt_set_error("gemm: unsupported dtype");
         return MEBT_EDTYPE;
     }
+    // split-K accumulates with fp32 atomics into a zeroed C
+    if (split > 1 && !p.beta) MEBT_HIP_CHECK(hipMemset2DAsync(p.C, (size_t)p.ldc * 4, 0, (size_t)p.N * 4, p.M, stream));
+    if (int rc = S > 1 ? launch_splitk(p, *k, S, stream) : launch_single(p, *k, split, stream)) return rc;
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
 
+static int launch_pair(GemmPair& g, const GemmConfig& c, hipStream_t stream) {
+    const GemmKernel* k = gemm_find(tables_of(true, g.p[0].b_kc).pair, GemmVariant::dma, c.tbm, c.tbn, c.ring);
+    if (!k) return no_kernel("gemm pair", c);
+    int tiles[2];
+    for (int i = 0; i < 2; ++i) {
+        g.ntx[i] = (g.p[i].N + k->tbn - 1) / k->tbn;
+        tiles[i] = ((g.p[i].M + k->tbm - 1) / k->tbm) * g.ntx[i];
+    }
+    g.tiles0 = tiles[0];
+    void* args[] = {&g};
+    return launch_kernel(*k, dim3(tiles[0] + tiles[1]), args, stream);
+}
+
 int launch_gemm_pair(const GemmParams& p0, const GemmParams& p1, int dtype, hipStream_t stream) {
     const bool ok = dtype == MEBT_BF16 && p0.a_kc && p1.a_kc && p0.b_kc == p1.b_kc && p0.M > 0 && p0.N > 0 && p1.M > 0 && p1.N > 0 &&
-                    p0.K > 0 && p1.K > 0 && !p0.beta && !p1.beta && !p0.c_f32 && !p1.c_f32 && !g_gemm_force_tile && g_gemm_dma < 0 &&
+                    p0.K > 0 && p1.K > 0 && !p0.beta && !p1.beta && !p0.c_f32 && !p1.c_f32 && !g_gemm_force_tbm && g_gemm_dma < 0 &&
                     p0.K % BK == 0 && p1.K % BK == 0 && p0.N % 8 == 0 && p1.N % 8 == 0 && !g_gemm_nostore;
-    if (!ok) {                       // anything unusual: two ordinary launches (with their own validation)
-        if (int rc = launch_gemm(p0, dtype, stream)) return rc;
-        return launch_gemm(p1, dtype, stream);
-    }
+    auto separate = [&] {            // the two products as ordinary launches, each with its own validation and configuration
+        const int rc = launch_gemm(p0, dtype, stream);
+        return rc ? rc : launch_gemm(p1, dtype, stream);
+    };
+    if (!ok) return separate();      // anything unusual
     GemmPair g;
     g.p[0] = p0; g.p[1] = p1;
-    int tbm = 96, tbn = 128, staging = 3;
     int choice = -1;
     {
         std::unique_lock<std::mutex> lk(g_tune_mutex);
@@ -611,40 +618,45 @@ int launch_gemm_pair(const GemmParams& p0, const GemmParams& p1, int dtype, hipS
             TuneRun tr;
             if (int rc = tr.begin(scratch_of(p0.scratch))) return rc;
             lk.unlock();            // the separate-launch baseline below goes through launch_gemm, which takes the lock itself
-            static const int tiles[7][2] = {{192, 128}, {128, 128}, {96, 128}, {128, 64}, {64, 128}, {96, 64}, {64, 64}};
-            float best = 1e30f;
-            std::vector<std::pair<int, float>> alts;
-            for (int t = 0; t < 7; ++t)
-                for (int st = 2; st <= 4; ++st) {
-                    if (st * (tiles[t][0] + tiles[t][1]) * BK * 2 > 128 * 1024) continue;
-                    float ms = 0.f;
-                    if (int rc = time_cold([&] { launch_pair_config(g, tiles[t][0], tiles[t][1], st, stream); }, stream, tr, ms)) return rc;
-                    alts.emplace_back((tiles[t][0] << 20) | (tiles[t][1] << 8) | st, ms);
-                    if (ms < best) { best = ms; tbm = tiles[t][0]; tbn = tiles[t][1]; staging = st; }
-                }
+            const GemmTable& t = tables_of(true, p0.b_kc).pair;
+            std::vector<TuneCand> cands;
+            for (int i = 0; i < t.n; ++i) cands.push_back({GemmConfig{t.k[i].tbm, t.k[i].tbn, t.k[i].ring}.encode(), 0.f});
+            int best;
+            if (int rc = tune_sweep(cands, [&](int code) { return launch_pair(g, GemmConfig::decode(code), stream); }, stream, tr, "pair ", best)) return rc;
+            const int fused = best >= 0 ? cands[best].code : GemmConfig{96, 128, 3}.encode();
+            const float best_ms = best >= 0 ? cands[best].ms : 1e30f;
             // ... against the two products launched one after the other with their own tuned configurations
             float sep = 0.f;
-            if (int rc = time_cold([&] { launch_gemm(p0, MEBT_BF16, stream); launch_gemm(p1, MEBT_BF16, stream); }, stream, tr, sep)) return rc;
-            if (int rc = time_cold([&] { launch_gemm(p0, MEBT_BF16, stream); launch_gemm(p1, MEBT_BF16, stream); }, stream, tr, sep)) return rc;
+            if (int rc = time_cold(separate, stream, tr, sep)) return rc;
+            if (int rc = time_cold(separate, stream, tr, sep)) return rc;
             if (g_tune_log)
-                fprintf(stderr, "[mebt gemm autotune] pair %dx%dx%d + %dx%dx%d b_kc=%d -> %dx%d ring %d (%.1f us cold; separate launches %.1f us)\n",
-                        p0.M, p0.N, p0.K, p1.M, p1.N, p1.K, p0.b_kc, tbm, tbn, staging, best * 1e3f, sep * 1e3f);
+                fprintf(stderr, "[mebt gemm autotune] pair %dx%dx%d + %dx%dx%d b_kc=%d -> %s (%.1f us cold; separate launches %.1f us)\n",
+                        p0.M, p0.N, p0.K, p1.M, p1.N, p1.K, p0.b_kc, describe(fused).c_str(), best_ms * 1e3f, sep * 1e3f);
             lk.lock();
-            alts.emplace_back(0, sep);                 // value 0 = the two products launched separately
-            alts_keep(key, alts);
-            it = g_tuned.emplace(key, sep <= best ? 0 : ((tbm << 20) | (tbn << 8) | staging)).first;
-            tune_remember(key, it->second);
+            cands.push_back({0, sep});                 // value 0 = the two products launched separately
+            it = tune_record(key, cands, sep <= best_ms ? 0 : fused);
         }
         if (it != g_tuned.end()) choice = it->second;
     }
-    if (choice == 0) {           // the pair did not win on this shape
-        if (int rc = launch_gemm(p0, dtype, stream)) return rc;
-        return launch_gemm(p1, dtype, stream);
-    }
-    if (choice > 0) { tbm = choice >> 20; tbn = (choice >> 8) & 0xFFF; staging = choice & 255; }
-    launch_pair_config(g, tbm, tbn, staging, stream);
+    if (choice == 0) return separate();           // the pair did not win on this shape
+    if (int rc = launch_pair(g, choice > 0 ? GemmConfig::decode(choice) : GemmConfig{96, 128, 3}, stream)) return rc;
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
+}
+
+// grouped weight gradients of one block (or two): one grid over the tiles of every item, in item order
+static int launch_grouped(GroupedWgrad& c, const GemmConfig& cfg, hipStream_t stream) {
+    const GemmKernel* k = gemm_find(tables_of(false, false).grouped, GemmVariant::dma, cfg.tbm, cfg.tbn, cfg.ring);
+    if (!k) return no_kernel("grouped wgrad", cfg);
+    int tiles = 0;
+    for (int i = 0; i < c.n; ++i) {
+        c.g[i].ntx = (c.g[i].N + k->tbn - 1) / k->tbn;
+        c.tile_start[i] = tiles;
+        tiles += ((c.g[i].M + k->tbm - 1) / k->tbm) * c.g[i].ntx;
+    }
+    for (int i = c.n; i <= MEBT_MAX_GROUP; ++i) c.tile_start[i] = tiles;
+    void* args[] = {&c};
+    return launch_kernel(*k, dim3(tiles), args, stream);
 }
 
 int launch_wgrad_grouped(GroupedWgrad& w, int dtype, hipStream_t stream) {
@@ -657,11 +669,13 @@ int launch_wgrad_grouped(GroupedWgrad& w, int dtype, hipStream_t stream) {
     }
     c.n = n;
     if (!n) return MEBT_OK;
-    c.beta = w.beta; c.scratch = w.scratch; c.Cb = w.Cb; c.gW = w.gW;
+    c.beta = w.beta; c.scratch = w.scratch; c.Cb = w.Cb;
     c.fused = w.fused; c.W = w.W; c.gW = w.gW; c.mW = w.mW; c.vW = w.vW; c.Wlp = w.Wlp; c.opt = w.opt;
-    for (int i = 1; i < n; ++i)              // insertion sort, K descending: the canonical order of the tuner key (the launchers order the items themselves)
+    // Insertion sort, K descending: the canonical order of the tuner key, and the launch order.  The key projection reduces over twice
+    // as many tokens as the rest: started last, its tiles were the tail of the launch.
+    for (int i = 1; i < n; ++i)
         for (int j = i; j > 0 && c.g[j].K > c.g[j - 1].K; --j) { const GroupedWgrad::Item t = c.g[j]; c.g[j] = c.g[j - 1]; c.g[j - 1] = t; }
-    int tbm = 128, tbn = 128, stages = g_grouped_stages == 3 ? 3 : 2;
+    GemmConfig cfg{128, 128, g_grouped_stages == 3 ? 3 : 2};
     {
         std::lock_guard<std::mutex> lk(g_tune_mutex);
         tune_init();
@@ -671,33 +685,26 @@ int launch_wgrad_grouped(GroupedWgrad& w, int dtype, hipStream_t stream) {
         if (it == g_tuned.end() && g_autotune && !c.beta && tune_scratch_of(w.scratch)) {
             TuneRun tr;
             if (int rc = tr.begin(scratch_of(w.scratch))) return rc;
-            static const int tiles[5][2] = {{256, 128}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};
-            float best = 1e30f;
             // candidates are timed in the mode that will run; a fused launch is not idempotent, so its candidates
             // run with a zero learning rate, zero decay and beta1 = beta2 = 1 (p, m, v are rewritten unchanged)
             GroupedWgrad tc = c;
             for (int i = 0; i < n; ++i) tc.g[i].bias = nullptr;      // the bias row sums are atomic adds: not in the repeated candidate runs
             if (tc.fused) { tc.opt.lr = 0.f; tc.opt.weight_decay = 0.f; tc.opt.beta1 = 1.f; tc.opt.beta2 = 1.f; }
-            std::vector<std::pair<int, float>> alts;
-            for (int t = 0; t < 5; ++t)
-                for (int st = 2; st <= 4; ++st) {
-                    if (tiles[t][0] == 256 && st > 3) continue;            // 8-wave 256 x 128: ring 2 or 3 (4 x 48 KiB does not fit the 160 KiB LDS)
-                    float ms = 0.f;
-                    if (int rc = time_cold([&] { launch_grouped_config(tc, tiles[t][0], tiles[t][1], st, stream); }, stream, tr, ms)) return rc;
-                    alts.emplace_back((tiles[t][0] << 20) | (tiles[t][1] << 8) | st, ms);
-                    if (g_tune_log >= 2) fprintf(stderr, "    cand grouped %dx%d ring %d%s%s: %.1f us\n", tiles[t][0], tiles[t][1], st, tc.fused ? " +adamw" : "", tc.Cb ? " bf16-out" : "", ms * 1e3f);
-                    if (ms < best) { best = ms; tbm = tiles[t][0]; tbn = tiles[t][1]; stages = st; }
-                }
+            const GemmTable& t = tables_of(false, false).grouped;
+            std::vector<TuneCand> cands;
+            for (int i = 0; i < t.n; ++i) cands.push_back({GemmConfig{t.k[i].tbm, t.k[i].tbn, t.k[i].ring}.encode(), 0.f});
+            const std::string what = std::string("grouped") + (tc.fused ? " +adamw" : "") + (tc.Cb ? " bf16-out" : "") + " ";
+            int best;
+            if (int rc = tune_sweep(cands, [&](int code) { return launch_grouped(tc, GemmConfig::decode(code), stream); }, stream, tr, what.c_str(), best)) return rc;
+            if (best >= 0) cfg = GemmConfig::decode(cands[best].code);
             if (g_tune_log) {
                 fprintf(stderr, "[mebt gemm autotune] grouped wgrad");
                 for (int i = 0; i < n; ++i) fprintf(stderr, " %dx%dx%d", c.g[i].M, c.g[i].N, c.g[i].K);
-                fprintf(stderr, " -> %dx%d ring %d (%.1f us cold)\n", tbm, tbn, stages, best * 1e3f);
+                fprintf(stderr, " -> %s (%.1f us cold)\n", describe(cfg.encode()).c_str(), best >= 0 ? cands[best].ms * 1e3f : 1e33f);
             }
-            alts_keep(key, alts);
-            it = g_tuned.emplace(key, (tbm << 20) | (tbn << 8) | stages).first;
-            tune_remember(key, it->second);
+            it = tune_record(key, cands, cfg.encode());
         }
-        if (it != g_tuned.end()) { tbm = it->second >> 20; tbn = (it->second >> 8) & 0xFFF; stages = it->second & 255; }
+        if (it != g_tuned.end()) cfg = GemmConfig::decode(it->second);
     }
     {   // experiments (tools/env_ab_cached.sh): MEBT_GROUPED_FORCE=256x128x2 = that tile / ring for every grouped launch
         static const int env_force = [] {
@@ -705,17 +712,21 @@ int launch_wgrad_grouped(GroupedWgrad& w, int dtype, hipStream_t stream) {
             int a = 0, b = 0, r = 0;
             return (e && sscanf(e, "%dx%dx%d", &a, &b, &r) == 3 && a && b) ? ((a << 20) | (b << 8) | r) : 0;
         }();
-        if (env_force && !g_grouped_force) { tbm = env_force >> 20; tbn = (env_force >> 8) & 0xFFF; stages = env_force & 255; }
+        if (env_force && !g_grouped_force) cfg = GemmConfig::decode(env_force);
     }
-    if (g_grouped_force) { tbm = g_grouped_force >> 20; tbn = (g_grouped_force >> 8) & 0xFFF; stages = g_grouped_force & 255; }
-    launch_grouped_config(c, tbm, tbn, stages, stream);
+    if (g_grouped_force) cfg = GemmConfig::decode(g_grouped_force);
+    if (int rc = launch_grouped(c, cfg, stream)) return rc;
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
 
+// dynamic-LDS attributes of every bf16 kernel (called once per process)
 int gemm_init_attributes() {
-    if (int rc = mebt_gemm_attrs_kk()) return rc;
-    if (int rc = mebt_gemm_attrs_kr()) return rc;
-    if (int rc = mebt_gemm_attrs_rr()) return rc;
-    return mebt_gemm_attrs_rk();
+    for (int l = 0; l < 4; ++l) {
+        const GemmTables& t = tables_of(l >> 1, l & 1);
+        for (const GemmTable& tb : {t.single, t.pair, t.grouped})
+            for (int i = 0; i < tb.n; ++i)
+                if (tb.k[i].lds <= kMaxLds) MEBT_HIP_CHECK(hipFuncSetAttribute(tb.k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, tb.k[i].lds));
+    }
+    return MEBT_OK;
 }

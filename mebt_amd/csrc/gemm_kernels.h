@@ -1,4 +1,4 @@
-// MFMA GEMM kernels for gfx950 (device code + per-layout launch helpers; included by gemm.hip and the four
+// MFMA GEMM kernels for gfx950 (device code + the host's configuration type and kernel-table entry; included by gemm.hip and the four
 // per-layout translation units gemm_kk/kr/rr/rk.hip so that the instantiations compile in parallel):  C[M,N] = sum_k A(m,k) * B(n,k)  (+ fused epilogue)
 //
 // Replaces the implicit ATen dispatches behind nn.Linear forward/backward on the MeBT hot path
@@ -20,7 +20,7 @@
 // reference implementation of the same LDS images.  Variants on top: two pipelines per workgroup on
 // alternate k-tiles, two independent products per launch (pair), the grouped weight gradients of a block
 // (optionally with AdamW in the epilogue), split-K into fp32 slabs + a reduce/epilogue kernel.  The host
-// picks tile / ring depth / variant per GEMM signature by timing them in situ (autotune_config).
+// picks tile / ring depth / variant per GEMM signature by timing them in situ (gemm.hip: autotune_single).
 // Ragged edges are handled by buffer-resource bounds (OOB loads return 0).
 //
 // f32 kernel (parity mode): same tiling on v_mfma_f32_32x32x2_f32, which is an exact fp32 FMA
@@ -1251,233 +1251,64 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmParams p) {
 
 }  // namespace
 
-// LDS bytes of a two-pipeline (KS = 2) configuration; 0 = not available for this tile / ring depth
-static inline int ks2_lds(int tbm, int tbn, int ring) {
-    const bool tile_ok = (tbm == 96 && tbn == 64) || (tbm == 64 && tbn == 64) || (tbm == 96 && tbn == 128) || (tbm == 64 && tbn == 128) || (tbm == 128 && tbn == 64);
-    if (!tile_ok || ring < 2 || ring > 3) return 0;
-    const int bytes = 2 * ring * (tbm + tbn) * BK * 2;
-    const int need = 34 * 1024 + 4 * (tbm / 32) * (tbn / 32) * 1024;
-    return (bytes <= 160 * 1024 && bytes >= need) ? bytes : 0;
-}
-template <bool AK, bool BKC>
-static void layout_launch_ks2(const GemmParams& p, int tbm, int tbn, int ring, hipStream_t stream) {
-    const dim3 grid((p.N + tbn - 1) / tbn, (p.M + tbm - 1) / tbm, 1);
-    const int lds = ks2_lds(tbm, tbn, ring);
-#define KS2_T(TM_, TN_)                                                                                                        \
-    do {                                                                                                                               \
-        if (ring == 3) hipLaunchKernelGGL((gemm_bf16_dma_ks2_kernel<AK, BKC, TM_, TN_, 3>), grid, dim3(512), lds, stream, p);            \
-        else hipLaunchKernelGGL((gemm_bf16_dma_ks2_kernel<AK, BKC, TM_, TN_, 2>), grid, dim3(512), lds, stream, p);                      \
-    } while (0)
-#define KS2_L()                                                      \
-    do {                                                            \
-        if (tbm == 96 && tbn == 64) KS2_T(96, 64);         \
-        else if (tbm == 64 && tbn == 64) KS2_T(64, 64);    \
-        else if (tbm == 96 && tbn == 128) KS2_T(96, 128);  \
-        else if (tbm == 64 && tbn == 128) KS2_T(64, 128);  \
-        else KS2_T(128, 64);                               \
-    } while (0)
-    KS2_L();
-#undef KS2_L
-#undef KS2_T
-}
+// ------------------------------------------------------------------------------------------------
+// Host side: a configuration, and the kernel tables the dispatch in gemm.hip chooses from
+// ------------------------------------------------------------------------------------------------
+enum class GemmVariant : uint8_t { dma, reg, pipe, ks2, w8, pp, splitk2, splitk4 };
 
-// staging 8 + ring (10 .. 12): the software-pipelined main loop (gemm_tile_pipe), whole reduction per workgroup
-template <bool AK, bool BKC>
-static bool layout_launch_pipe(const GemmParams& p, int tbm, int tbn, int ring, hipStream_t stream) {
-    const dim3 grid((p.N + tbn - 1) / tbn, (p.M + tbm - 1) / tbm, 1);
-#define PIPE_T(TM_, TN_)                                                                                                                      \
-    do {                                                                                                                                      \
-        if (ring * (TM_ + TN_) * BK * 2 > 160 * 1024) return false;                                                                           \
-        if (ring >= 4) hipLaunchKernelGGL((gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 160 * 1024 ? 4 : 2)>), grid, dim3(256), 4 * (TM_ + TN_) * BK * 2, stream, p); \
-        else if (ring == 3) hipLaunchKernelGGL((gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, 3>), grid, dim3(256), 3 * (TM_ + TN_) * BK * 2, stream, p); \
-        else hipLaunchKernelGGL((gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, 2>), grid, dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, p);            \
-        return true;                                                                                                                          \
-    } while (0)
-    if (tbm == 128 && tbn == 128) PIPE_T(128, 128);
-    else if (tbm == 192 && tbn == 128) PIPE_T(192, 128);
-    else if (tbm == 96 && tbn == 128) PIPE_T(96, 128);
-    else if (tbm == 96 && tbn == 64) PIPE_T(96, 64);
-    else if (tbm == 128 && tbn == 64) PIPE_T(128, 64);
-    else if (tbm == 64 && tbn == 128) PIPE_T(64, 128);
-    else if (tbm == 64 && tbn == 64) PIPE_T(64, 64);
-#undef PIPE_T
-    return false;
-}
-
-template <bool AK, bool BKC>
-static void layout_launch_cfg(const GemmParams& p, int tbm, int tbn, int staging, int split, hipStream_t stream) {
-    if (staging >= 10 && staging <= 12 && split == 1 && !p.slab) {
-        if (layout_launch_pipe<AK, BKC>(p, tbm, tbn, staging - 8, stream)) return;
-        staging -= 8;
+// A bf16 GEMM configuration: block tile, LDS ring depth and main-loop variant.  The tune table (MEBT_TUNE_VERSION 4), its text form
+// and the debug entry points keep it packed as (tbm << 20) | (tbn << 8) | code, and encode() / decode() are the only code that knows
+// the packing.  The code byte:
+//      0       register-staged two-stage loop (reg)
+//      1 .. 7  LDS-DMA ring of that depth (dma; a forced 1 runs ring 3)
+//      8 + r   software-pipelined main loop, ring r (pipe)
+//     16 + r   two pipelines per workgroup on alternate k-tiles, ring r (ks2)
+//     32 + r   split-K into 2 fp32 slabs + splitk_reduce_kernel, ring r (splitk2)
+//     64 + r   the same with 4 slabs (splitk4)
+// With the 256 x 256 tile, 9 is the two staggered wave groups (pp) and any other code the 8-wave kernel (w8, ring = code).  Pair and
+// grouped entries are LDS-DMA rings (code = ring).  Codes of 100 and above never reach a table: mebt_debug_gemm_variant takes them
+// as "no C store" experiments.
+struct GemmConfig {
+    int tbm = 0, tbn = 0, ring = 0;
+    GemmVariant v = GemmVariant::dma;
+    int encode() const {
+        static constexpr int base[] = {0, 0, 8, 16, 0, 9, 32, 64};
+        return (tbm << 20) | (tbn << 8) | (base[(int)v] + (v == GemmVariant::reg || v == GemmVariant::pp ? 0 : ring));
     }
-    const dim3 grid((p.N + tbn - 1) / tbn, (p.M + tbm - 1) / tbm, split);
-#define LAUNCH_T(TM_, TN_)                                                                                           \
-        do {                                                                                                         \
-            if (staging == 5 && 5 * (TM_ + TN_) * BK * 2 <= 160 * 1024) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, (5 * (TM_ + TN_) * BK * 2 <= 160 * 1024 ? 5 : 2)>), grid, dim3(256), 5 * (TM_ + TN_) * BK * 2, stream, p); \
-            else if (staging >= 4) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 4>), grid, dim3(256), 4 * (TM_ + TN_) * BK * 2, stream, p); \
-            else if (staging == 3) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 3>), grid, dim3(256), 3 * (TM_ + TN_) * BK * 2, stream, p); \
-            else if (staging == 2) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 2>), grid, dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, p); \
-            else hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKC, TM_, TN_>), grid, dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, p);          \
-        } while (0)
-        /* tiles that exist as LDS-DMA kernels only (2..4 stages) */
-#define LAUNCH_D(TM_, TN_)                                                                                           \
-        do {                                                                                                         \
-            if (staging >= 4 && 4 * (TM_ + TN_) * BK * 2 <= 128 * 1024) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024 ? 4 : 2)>), grid, dim3(256), 4 * (TM_ + TN_) * BK * 2, stream, p); \
-            else if (staging >= 3) hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 3>), grid, dim3(256), 3 * (TM_ + TN_) * BK * 2, stream, p); \
-            else hipLaunchKernelGGL((gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 2>), grid, dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, p); \
-        } while (0)
-#define LAUNCH_BF16()                                                  \
-        do {                                                           \
-            if (tbm == 128 && tbn == 128) LAUNCH_T(128, 128); \
-            else if (tbm == 192 && tbn == 128) LAUNCH_D(192, 128); \
-            else if (tbm == 96 && tbn == 128) LAUNCH_D(96, 128); \
-            else if (tbm == 96 && tbn == 64) LAUNCH_D(96, 64); \
-            else if (tbm == 128 && tbn == 64) LAUNCH_T(128, 64); \
-            else if (tbm == 64 && tbn == 128) LAUNCH_T(64, 128); \
-            else LAUNCH_T(64, 64);                            \
-        } while (0)
-    LAUNCH_BF16();
-#undef LAUNCH_BF16
-#undef LAUNCH_D
-#undef LAUNCH_T
-}
-
-template <bool AK, bool BKC>
-static void layout_launch_pair(GemmPair& g, int tbm, int tbn, int staging, hipStream_t stream) {
-    int tiles[2];
-    for (int i = 0; i < 2; ++i) {
-        g.ntx[i] = (g.p[i].N + tbn - 1) / tbn;
-        tiles[i] = ((g.p[i].M + tbm - 1) / tbm) * g.ntx[i];
+    static GemmConfig decode(int code) {
+        const int s = code & 255;
+        GemmConfig c;
+        c.tbm = code >> 20;
+        c.tbn = (code >> 8) & 0xFFF;
+        if (c.tbm == 256 && c.tbn == 256) { c.v = s == 9 ? GemmVariant::pp : GemmVariant::w8; c.ring = s == 9 ? 0 : s; }
+        else if (s == 0) c.v = GemmVariant::reg;
+        else if (s < 8) { c.v = GemmVariant::dma; c.ring = s; }
+        else if (s < 16) { c.v = GemmVariant::pipe; c.ring = s - 8; }
+        else if (s < 32) { c.v = GemmVariant::ks2; c.ring = s - 16; }
+        else if (s < 64) { c.v = GemmVariant::splitk2; c.ring = s - 32; }
+        else { c.v = GemmVariant::splitk4; c.ring = s - 64; }
+        return c;
     }
-    g.tiles0 = tiles[0];
-    const dim3 grid(tiles[0] + tiles[1]);
-#define PAIR_T(TM_, TN_)                                                                                                                                  \
-    do {                                                                                                                                                  \
-        if (staging >= 4 && 4 * (TM_ + TN_) * BK * 2 <= 128 * 1024) hipLaunchKernelGGL((gemm_pair_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024 ? 4 : 2)>), grid, dim3(256), 4 * (TM_ + TN_) * BK * 2, stream, g); \
-        else if (staging >= 3) hipLaunchKernelGGL((gemm_pair_kernel<AK, BKC, TM_, TN_, 3>), grid, dim3(256), 3 * (TM_ + TN_) * BK * 2, stream, g);          \
-        else hipLaunchKernelGGL((gemm_pair_kernel<AK, BKC, TM_, TN_, 2>), grid, dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, g);                           \
-    } while (0)
-#define PAIR_L()                                                         \
-    do {                                                                 \
-        if (tbm == 128 && tbn == 128) PAIR_T(128, 128);         \
-        else if (tbm == 192 && tbn == 128) PAIR_T(192, 128);    \
-        else if (tbm == 96 && tbn == 128) PAIR_T(96, 128);      \
-        else if (tbm == 96 && tbn == 64) PAIR_T(96, 64);        \
-        else if (tbm == 128 && tbn == 64) PAIR_T(128, 64);      \
-        else if (tbm == 64 && tbn == 128) PAIR_T(64, 128);      \
-        else PAIR_T(64, 64);                                    \
-    } while (0)
-    PAIR_L();
-#undef PAIR_L
-#undef PAIR_T
-}
+};
 
-// grouped weight gradients of one block.  Items are ordered by reduction length, longest first (the key
-// projection reduces over twice as many tokens as the rest: started last, its tiles were the tail of the
-// launch), and the block tile / ring depth are autotuned per group signature like the single GEMMs.
-static void layout_launch_grouped(GroupedWgrad& c, int tbm, int tbn, int stages, hipStream_t stream) {
-    for (int i = 1; i < c.n; ++i)              // insertion sort, K descending (longest reduction first: its tiles are not the tail)
-        for (int j = i; j > 0 && c.g[j].K > c.g[j - 1].K; --j) { const GroupedWgrad::Item t = c.g[j]; c.g[j] = c.g[j - 1]; c.g[j - 1] = t; }
-    int tiles = 0;
-    for (int i = 0; i < c.n; ++i) {
-        c.g[i].ntx = (c.g[i].N + tbn - 1) / tbn;
-        c.tile_start[i] = tiles;
-        tiles += ((c.g[i].M + tbm - 1) / tbm) * c.g[i].ntx;
-    }
-    for (int i = c.n; i <= MEBT_MAX_GROUP; ++i) c.tile_start[i] = tiles;
-#define LAUNCH_G(TM_, TN_)                                                                                                                   \
-    do {                                                                                                                                    \
-        if (stages >= 4) hipLaunchKernelGGL((wgrad_grouped_kernel<TM_, TN_, 4>), dim3(tiles), dim3(256), 4 * (TM_ + TN_) * BK * 2, stream, c);      \
-        else if (stages == 3) hipLaunchKernelGGL((wgrad_grouped_kernel<TM_, TN_, 3>), dim3(tiles), dim3(256), 3 * (TM_ + TN_) * BK * 2, stream, c); \
-        else hipLaunchKernelGGL((wgrad_grouped_kernel<TM_, TN_, 2>), dim3(tiles), dim3(256), 2 * (TM_ + TN_) * BK * 2, stream, c);                 \
-    } while (0)
-    if (tbm == 256 && tbn == 128) {          // eight waves, one workgroup per CU (ring 2: 96 KiB, ring 3: 144 KiB)
-        if (stages >= 3) hipLaunchKernelGGL((wgrad_grouped_kernel<256, 128, 3, 8>), dim3(tiles), dim3(512), 3 * 384 * BK * 2, stream, c);
-        else hipLaunchKernelGGL((wgrad_grouped_kernel<256, 128, 2, 8>), dim3(tiles), dim3(512), 2 * 384 * BK * 2, stream, c);
-    }
-    else if (tbm == 128 && tbn == 128) LAUNCH_G(128, 128);
-    else if (tbm == 128 && tbn == 64) LAUNCH_G(128, 64);
-    else if (tbm == 64 && tbn == 128) LAUNCH_G(64, 128);
-    else LAUNCH_G(64, 64);
-#undef LAUNCH_G
-}
+// One kernel instantiation: what a resolver picks, what gets launched (hipLaunchKernel on `fn`) and what gets its LDS attribute.
+struct GemmKernel {
+    GemmVariant v;
+    int tbm, tbn, ring, threads;
+    int lds;                        // dynamic LDS bytes of a launch; an entry above kMaxLds is never launched
+    const void* fn;
+};
+struct GemmTable { const GemmKernel* k; int n; };
+// The tables of one operand layout, defined by its unit (gemm_layout.inc): pair kernels exist for A KC only, grouped ones for RC x RC.
+struct GemmTables { GemmTable single, pair, grouped; };
+GemmTables mebt_gemm_tables_kk();
+GemmTables mebt_gemm_tables_kr();
+GemmTables mebt_gemm_tables_rr();
+GemmTables mebt_gemm_tables_rk();
 
-template <bool AK, bool BKC>
-static void layout_launch_w8(const GemmParams& p, int ring, hipStream_t stream) {
-    const dim3 grid((p.N + 255) / 256, (p.M + 255) / 256, 1);
-    if (ring >= 3) return;                          // 3 x 64 KiB does not fit the 160 KiB LDS: ring 2 only
-    hipLaunchKernelGGL((gemm_bf16_w8_kernel<AK, BKC, 2>), grid, dim3(512), 2 * 512 * BK * 2, stream, p);
-}
-
-// the staggered two-group 256 x 256 kernel: A KC only, K a multiple of 64
-template <bool AK, bool BKC>
-static void layout_launch_pp(const GemmParams& p, hipStream_t stream) {
-    const int tiles = ((p.N + 255) / 256) * ((p.M + 255) / 256);
-    const dim3 grid(tiles < 256 ? tiles : 256, 1, 1);          // persistent over the tile list: one workgroup per CU
-    if (AK) hipLaunchKernelGGL((gemm_bf16_pp_kernel<BKC>), grid, dim3(512), 8 * 128 * BK * 2 + 8 * 4096, stream, p);
-}
-
-// dynamic-LDS attributes of every instantiation of one operand layout (called once per process)
-template <bool AK, bool BKC>
-static int layout_set_attrs() {
-#define SET_T(TM_, TN_)                                                                                                  \
-    do {                                                                                                                         \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<AK, BKC, TM_, TN_>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TM_ + TN_) * BK * 2)); \
-        if (5 * (TM_ + TN_) * BK * 2 <= 160 * 1024) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, (5 * (TM_ + TN_) * BK * 2 <= 160 * 1024 ? 5 : 2)>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (TM_ + TN_) * BK * 2)); \
-    } while (0)
-#define SET_D(TM_, TN_)                                                                                                  \
-    do {                                                                                                                         \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (TM_ + TN_) * BK * 2)); \
-        if (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024 ? 4 : 2)>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TM_ + TN_) * BK * 2)); \
-    } while (0)
-#define SET_K(TM_, TN_)                                                                                                                           \
-    do {                                                                                                                                                  \
-        if (ks2_lds(TM_, TN_, 2)) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_ks2_kernel<AK, BKC, TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, ks2_lds(TM_, TN_, 2))); \
-        if (ks2_lds(TM_, TN_, 3)) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_dma_ks2_kernel<AK, BKC, TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, ks2_lds(TM_, TN_, 3))); \
-    } while (0)
-    SET_T(128, 128); SET_T(128, 64); SET_T(64, 128); SET_T(64, 64); SET_D(192, 128); SET_D(96, 128); SET_D(96, 64);
-#define SET_PIPE(TM_, TN_)                                                                                                       \
-    do {                                                                                                                         \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (TM_ + TN_) * BK * 2)); \
-        if (4 * (TM_ + TN_) * BK * 2 <= 160 * 1024) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pipe_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 160 * 1024 ? 4 : 2)>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TM_ + TN_) * BK * 2)); \
-    } while (0)
-    SET_PIPE(128, 128); SET_PIPE(192, 128); SET_PIPE(96, 128); SET_PIPE(96, 64); SET_PIPE(128, 64); SET_PIPE(64, 128); SET_PIPE(64, 64);
-#undef SET_PIPE
-    MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_w8_kernel<AK, BKC, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * BK * 2));
-    if (AK) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_pp_kernel<BKC>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 128 * BK * 2 + 8 * 4096));
-    SET_K(96, 64); SET_K(64, 64); SET_K(96, 128); SET_K(64, 128); SET_K(128, 64);
-#undef SET_K
-#undef SET_D
-#undef SET_T
-    return MEBT_OK;
-}
-template <bool AK, bool BKC>
-static int layout_set_pair_attrs() {
-#define SET_P(TM_, TN_)                                                                                                                           \
-    do {                                                                                                                                                  \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pair_kernel<AK, BKC, TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pair_kernel<AK, BKC, TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (TM_ + TN_) * BK * 2)); \
-        if (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024) MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pair_kernel<AK, BKC, TM_, TN_, (4 * (TM_ + TN_) * BK * 2 <= 128 * 1024 ? 4 : 2)>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TM_ + TN_) * BK * 2)); \
-    } while (0)
-    SET_P(192, 128); SET_P(128, 128); SET_P(96, 128); SET_P(128, 64); SET_P(64, 128); SET_P(96, 64); SET_P(64, 64);
-#undef SET_P
-    return MEBT_OK;
-}
-static int layout_set_grouped_attrs() {
-#define SET_G(TM_, TN_)                                                                                                                                        \
-    do {                                                                                                                                                  \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<TM_, TN_, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<TM_, TN_, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * (TM_ + TN_) * BK * 2)); \
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<TM_, TN_, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (TM_ + TN_) * BK * 2)); \
-    } while (0)
-    SET_G(128, 128); SET_G(128, 64); SET_G(64, 128); SET_G(64, 64);
-#undef SET_G
-    MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<256, 128, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 384 * BK * 2));
-    MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_grouped_kernel<256, 128, 3, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 384 * BK * 2));
-    return MEBT_OK;
+constexpr int kMaxLds = 160 * 1024;
+// LDS of a two-pipeline kernel: its two rings, which the epilogue reuses for the exchange of the partial sums (34 KiB + 4 KiB per
+// 32 x 32 sub-tile).  A tile whose rings are smaller than that gets a size above kMaxLds, i.e. never runs.
+constexpr int ks2_lds(int tbm, int tbn, int ring) {
+    return 2 * ring * (tbm + tbn) * BK * 2 >= 34 * 1024 + 4 * (tbm / 32) * (tbn / 32) * 1024 ? 2 * ring * (tbm + tbn) * BK * 2 : kMaxLds + 1;
 }

@@ -227,6 +227,27 @@ def test_gemm_splitk_slabs_with_epilogues(tile, variant, b_kc):
         lib().mebt_debug_gemm_scratch(None, 0)
 
 
+MEBT_STATUS_EINVAL = 1      # include/mebt_hip.h
+
+
+def test_gemm_forced_tile_without_kernel_is_rejected():
+    """a forced block tile that no bf16 kernel exists for (256 x 128, LDS-DMA ring 2) fails with MEBT_STATUS_EINVAL and writes nothing
+    (it used to run the 64 x 64 kernel on a grid laid out for the requested tile: part of C unwritten, status OK)"""
+    M, N, K = 512, 256, 128
+    A = rnd(M, K, seed=41, ints=True).to(DEV, torch.bfloat16)
+    B = rnd(N, K, seed=42, ints=True).to(DEV, torch.bfloat16)
+    Cd = torch.full((M, N), 7.0, device=DEV)
+    lib().mebt_debug_gemm_tile(256, 128)
+    lib().mebt_debug_gemm_variant(2)
+    try:
+        st = lib().mebt_op_gemm(_lib.BF16, ptr(A), ptr(B), ptr(Cd), None, None, None, M, N, K, K, K, N, N, 1, 1, 0, 1, 0, 1, cur_stream())
+    finally:
+        lib().mebt_debug_gemm_tile(0, 0)
+        lib().mebt_debug_gemm_variant(-1)
+    torch.cuda.synchronize()
+    assert st == MEBT_STATUS_EINVAL and b"256 x 128" in lib().mebt_last_error()
+    assert torch.all(Cd == 7.0)
+
 @pytest.mark.parametrize("dtype,tol", [(_lib.BF16, 2e-2), (_lib.F32, 1e-5)])
 @pytest.mark.parametrize("rows,d", [(37, 64), (130, 256), (64, 1024), (5, 320)])
 def test_layernorm_fwd_bwd(dtype, tol, rows, d):
@@ -759,3 +780,27 @@ def test_wgrad_grouped_operator(items, grouped_config):
         assert (W2[sl] - p_).abs().max().item() <= 2e-2 * lr, (no, ki, t, (W2[sl] - p_).abs().max().item())
         assert torch.equal(Wlp2[sl], W2[sl].to(torch.bfloat16))
         assert (b - bs).abs().max().item() <= 2e-4 * max(1.0, bs.abs().max().item())
+
+
+def test_wgrad_grouped_forced_tile_without_kernel_is_rejected():
+    """the grouped weight-gradient launch forced to a tile it has no kernel for (256 x 64, ring 2): MEBT_STATUS_EINVAL, gW untouched"""
+    import ctypes as C
+    items = [(256, 128, 200), (128, 512, 200)]
+    n = len(items)
+    g = torch.Generator().manual_seed(3)
+    dYs = [(torch.randn(t, no, generator=g) * 0.5).to(torch.bfloat16).to(DEV) for no, ki, t in items]
+    Xs = [(torch.randn(t, ki, generator=g) * 0.5).to(torch.bfloat16).to(DEV) for no, ki, t in items]
+    offs = [0, items[0][0] * items[0][1]]
+    gW = torch.full((sum(no * ki for no, ki, _ in items),), 7.0, device=DEV)
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    i32 = lambda vs: (C.c_int32 * n)(*vs)
+    lib().mebt_debug_grouped_config(256, 64, 2)
+    try:
+        st = lib().mebt_op_wgrad_grouped(n, arr(dYs), arr(Xs), i32([i[0] for i in items]), i32([i[1] for i in items]), i32([i[2] for i in items]),
+                                         (C.c_int64 * n)(*offs), None, None, ptr(gW), None, None, None, 0, 0.0, 0.9, 0.95, 1e-8, 0.0, 1, 1.0,
+                                         cur_stream())
+    finally:
+        lib().mebt_debug_grouped_config(0, 0, 0)
+    torch.cuda.synchronize()
+    assert st == MEBT_STATUS_EINVAL and b"256 x 64" in lib().mebt_last_error()
+    assert torch.all(gW == 7.0)

@@ -51,6 +51,19 @@ def test_shipped_tune_table_matches_this_build():
     assert out.stdout.split()[0] == "1", out.stdout
 
 
+def test_shipped_tune_values_survive_decode_encode():
+    """every value of the shipped table is read through GemmConfig::decode and kept as its encode(): exported again, the table is the
+    shipped text line for line (the packed format has one decoder, and it loses nothing the tuner wrote)"""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "from mebt_amd import _lib; print(_lib.tune_table_text(), end='')"
+    env = {k: v for k, v in os.environ.items() if k not in ("MEBT_GEMM_TUNE_CACHE", "MEBT_GEMM_TUNE_SHIPPED")}
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    with open(os.path.join(root, "mebt_amd", "tune", "gfx950.txt")) as f:
+        shipped = f.read().split("\n")
+    assert sorted(l for l in out.stdout.split("\n") if l) == sorted(l for l in shipped if l)
+
 def test_tune_cache_of_another_version_is_moved_aside_not_truncated(tmp_path):
     """MEBT_GEMM_TUNE_CACHE pointing at a table of another MEBT_TUNE_VERSION (or at a file that is no table at all): the file is kept
     as <cache>.v<its version>, a fresh versioned table starts by rename, under a lock several ranks take (the old code
