@@ -232,6 +232,16 @@ int mebt_op_wgrad_grouped(int32_t n, const void* const* dY, const void* const* X
                           const int32_t* tokens, const int64_t* w_off, float* const* bias, float* W, float* gW, float* mW, float* vW,
                           void* Wlp, int32_t fused, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
                           float grad_scale, mebt_stream_t stream);
+/* Tests: two independent bf16 products in ONE launch, as the engine issues the q and k|v projections of a block (forward and dgrad).
+ * Every per-product argument is an array of two: C_i[M_i, N_i] = A_i B_i^T + bias_i, A_i stored [M_i][K_i] (row stride lda_i), B_i stored
+ * [N_i][K_i] (b_kc = 1) or [K_i][N_i] (b_kc = 0, both products alike), epilogue_i 0 none / 2 + aux_i residual / 3 * gelu'(aux_i) (there is no
+ * C2, so no GELU), c_f32_i != 0: fp32 C_i.  bias / aux may be NULL or hold NULLs.  One pair kernel runs when both outputs are bf16, every
+ * K_i is a multiple of 64, every N_i a multiple of 8 and no single-product tile / variant is forced; otherwise the products go out as
+ * two ordinary launches under the rules of mebt_op_gemm.  Null operands and bad epilogues are MEBT_STATUS_EINVAL, bad extents
+ * MEBT_STATUS_ESHAPE, before anything is launched. */
+int mebt_op_gemm_pair(const void* const* A, const void* const* B, void* const* C, const float* const* bias, const void* const* aux,
+                      const int32_t* M, const int32_t* N, const int32_t* K, const int32_t* lda, const int32_t* ldb, const int32_t* ldc,
+                      const int32_t* ld_aux, const int32_t* epilogue, const int32_t* c_f32, int32_t b_kc, mebt_stream_t stream);
 /* kth[r] = the top_k-th largest value of row r of logits [rows, V] (1 <= top_k < V): the threshold of the reference's module-level
  * `top_k_logits` (transformer.py:891-895: everything below it becomes -inf, ties are kept).  ids_scratch: [rows] int64. */
 int mebt_op_topk_threshold(const float* logits, int32_t top_k, float* kth, int64_t* ids_scratch, int32_t rows, int32_t V,
@@ -418,6 +428,17 @@ int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int32_t xcd, in
  * 2-4; 256x128 with ring 2-3; a deeper ring is clamped) instead of the tuned / shipped choice, any other tile makes the launch fail with
  * MEBT_STATUS_EINVAL; tbm = 0 switches the override off. */
 void mebt_debug_grouped_config(int32_t tbm, int32_t tbn, int32_t ring);
+/* Tests only: while set, every launch that qualifies as a pair (mebt_op_gemm_pair) skips the tune table and runs the pair kernel of this
+ * tile (192x128 with ring 2-3; 128x128, 96x128, 128x64, 64x128, 96x64 or 64x64 with ring 2-4; a deeper ring is clamped); any other tile
+ * makes the launch fail with MEBT_STATUS_EINVAL and write nothing.  Products that do not qualify still go out as two ordinary
+ * launches.  tbm = 0 switches the override off. */
+void mebt_debug_pair_config(int32_t tbm, int32_t tbn, int32_t ring);
+/* Tests only: the number of GEMM-family kernel launches (tuner candidates included) since the previous call; resets the count.  out[0..8)
+ * describes the last of them: {family (0 single product, 1 pair, 2 grouped weight gradients, 3 split-K reduce; -1: none since the
+ * previous call), code byte of the kernel that ran (see mebt_debug_gemm_variant; taken from its table entry, not from the request: the
+ * 8-wave 256 x 256 kernel is 2, the fp32 kernels 0, the reduce kernels 32 / 64), block tile rows, block tile columns, threads per
+ * workgroup, grid x, grid y, grid z}.  Process-wide and unsynchronised, like the other debug hooks. */
+int32_t mebt_debug_gemm_last_launch(int32_t out[8]);
 /* Benchmarking only: LDS-DMA ring depth (2 or 3) of the grouped weight-gradient GEMM. */
 void mebt_debug_grouped_stages(int32_t n);
 

@@ -69,6 +69,7 @@ PROTOTYPES = {
     "mebt_op_sample_lp": (c_i32, [c_vp, c_i32, c_vp, C.c_uint64, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_wgrad_grouped": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32,
                                       c_f32, c_f32, c_i32, c_f32, c_vp]),
+    "mebt_op_gemm_pair": (c_i32, [c_vp] * 14 + [c_i32, c_vp]),
     "mebt_op_topk_threshold": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mebt_op_scatter_ids": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_next_mask": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
@@ -94,6 +95,8 @@ PROTOTYPES = {
     "mebt_debug_gemm_scratch": (None, [c_vp, c_i64]),
     "mebt_debug_gemm_stamps": (None, [c_vp]),
     "mebt_debug_grouped_config": (None, [c_i32, c_i32, c_i32]),
+    "mebt_debug_pair_config": (None, [c_i32, c_i32, c_i32]),
+    "mebt_debug_gemm_last_launch": (c_i32, [C.POINTER(c_i32)]),
     "mebt_debug_attn_dropout": (None, [C.c_uint64, c_f32, c_vp]),
     "mebt_debug_attn_legacy": (None, [c_i32]),
     "mebt_debug_attn_block_order": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),

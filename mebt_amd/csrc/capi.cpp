@@ -33,6 +33,31 @@ extern "C" int mebt_op_gemm(int32_t dtype, const void* A, const void* B, void* C
     return launch_gemm(p, dtype, S(stream));
 }
 
+// The pair launch as an operator (tests): products i = 0, 1 are C_i[M_i, N_i] = A_i B_i^T + bias_i (+ epilogue_i), bf16 with A stored
+// [rows][K]; both B operands share b_kc.  Every per-product argument is an array of two.  There is no C2: epilogue 0 none, 2 + aux
+// residual, 3 * gelu'(aux).  Products launch_gemm_pair does not take as a pair go out as two ordinary launches.
+extern "C" int mebt_op_gemm_pair(const void* const* A, const void* const* B, void* const* C, const float* const* bias, const void* const* aux,
+                                 const int32_t* M, const int32_t* N, const int32_t* K, const int32_t* lda, const int32_t* ldb,
+                                 const int32_t* ldc, const int32_t* ld_aux, const int32_t* epilogue, const int32_t* c_f32, int32_t b_kc,
+                                 mebt_stream_t stream) {
+    if (!A || !B || !C || !M || !N || !K || !lda || !ldb || !ldc || !ld_aux || !epilogue || !c_f32) { mebt_set_error("gemm pair: bad arguments"); return MEBT_EINVAL; }
+    GemmParams p[2];
+    memset(p, 0, sizeof(p));
+    for (int i = 0; i < 2; ++i) {
+        if (!A[i] || !B[i] || !C[i]) { mebt_set_error("gemm pair: null operand"); return MEBT_EINVAL; }
+        if (epilogue[i] != EPI_NONE && epilogue[i] != EPI_RESID && epilogue[i] != EPI_GELU_BWD) { mebt_set_error("gemm pair: bad epilogue (0, 2 or 3: there is no C2)"); return MEBT_EINVAL; }
+        if (epilogue[i] != EPI_NONE && !(aux && aux[i])) { mebt_set_error("gemm pair: epilogue needs aux"); return MEBT_EINVAL; }
+        if (M[i] < 0 || N[i] < 0 || K[i] <= 0) { mebt_set_error("gemm pair: bad extents"); return MEBT_ESHAPE; }
+        GemmParams& q = p[i];
+        q.A = A[i]; q.B = B[i]; q.C = C[i]; q.bias = bias ? bias[i] : nullptr; q.aux = aux ? aux[i] : nullptr; q.M = M[i]; q.N = N[i]; q.K = K[i];
+        q.lda = lda[i]; q.ldb = ldb[i]; q.ldc = ldc[i]; q.ld_aux = ld_aux[i]; q.a_kc = 1; q.b_kc = b_kc ? 1 : 0;
+        q.epilogue = epilogue[i]; q.c_f32 = c_f32[i] ? 1 : 0; q.split_k = 1;
+    }
+    static bool inited = false;
+    if (!inited) { if (int rc = gemm_init_attributes()) return rc; inited = true; }
+    return launch_gemm_pair(p[0], p[1], MEBT_BF16, S(stream));
+}
+
 // The grouped weight-gradient launch of one block as an operator (tests, benchmarks): item i is dW_i[n_out_i, k_in_i] = dY_i^T X_i over
 // tokens_i rows (dY_i [tokens, n_out] bf16, X_i [tokens, k_in] bf16), written at gW + w_off[i] (fp32); bias[i] (or NULL) += column sums of
 // dY_i.  fused != 0: AdamW (torch semantics, step >= 1) is applied to W / mW / vW (+ the bf16 mirror Wlp) at the same offsets instead.

@@ -23,6 +23,8 @@ static int g_grouped_stages = 2;
 extern "C" void mebt_debug_grouped_stages(int n) { g_grouped_stages = n; }
 static int g_grouped_force = 0;       // a packed GemmConfig: tools/wgrad_bench.py times tile shapes the table does not hold
 extern "C" void mebt_debug_grouped_config(int32_t tbm, int32_t tbn, int32_t ring) { g_grouped_force = (tbm && tbn) ? ((tbm << 20) | (tbn << 8) | ring) : 0; }
+static int g_pair_force = 0;          // a packed GemmConfig: tests run every entry of the pair table, which the tune table only reaches at production shapes
+extern "C" void mebt_debug_pair_config(int32_t tbm, int32_t tbn, int32_t ring) { g_pair_force = (tbm && tbn) ? ((tbm << 20) | (tbn << 8) | ring) : 0; }
 static int g_gemm_dma = -1;           // -1 autotune / heuristic; forced (tests, tools): a GemmConfig code byte
 static int g_gemm_nostore = 0;        // experiments only (variant >= 100): skip the C store of plain epilogues
 extern "C" void mebt_debug_gemm_variant(int dma) { g_gemm_nostore = dma >= 100; g_gemm_dma = dma >= 100 ? (dma == 199 ? -1 : dma - 100) : dma; }
@@ -98,9 +100,25 @@ static int no_kernel(const char* family, const GemmConfig& c) {
     mebt_set_error(msg);
     return MEBT_EINVAL;
 }
-static int launch_kernel(const GemmKernel& k, dim3 grid, void** args, hipStream_t stream) {
+// Every launch of the GEMM family goes through launch_kernel, which keeps a count and the last launch for the tests
+// (mebt_debug_gemm_last_launch): which kernel ran, as its table entry describes it, not as it was asked for.
+enum GemmFamily { FAMILY_SINGLE = 0, FAMILY_PAIR = 1, FAMILY_GROUPED = 2, FAMILY_SPLITK_REDUCE = 3 };
+static int g_launch_count = 0;
+static int32_t g_last_launch[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
+static int launch_kernel(const GemmKernel& k, GemmFamily family, dim3 grid, void** args, hipStream_t stream) {
     MEBT_HIP_CHECK(hipLaunchKernel(k.fn, grid, dim3(k.threads), args, k.lds, stream));
+    ++g_launch_count;
+    const int32_t rec[8] = {family, GemmConfig{k.tbm, k.tbn, k.ring, k.v}.encode() & 255, k.tbm, k.tbn, k.threads, (int32_t)grid.x, (int32_t)grid.y, (int32_t)grid.z};
+    memcpy(g_last_launch, rec, sizeof rec);
     return MEBT_OK;
+}
+extern "C" int32_t mebt_debug_gemm_last_launch(int32_t out[8]) {
+    const int n = g_launch_count;
+    if (out) memcpy(out, g_last_launch, sizeof g_last_launch);
+    g_launch_count = 0;
+    g_last_launch[0] = -1;
+    for (int i = 1; i < 8; ++i) g_last_launch[i] = 0;
+    return n;
 }
 
 // What runs for configuration c on product p (split: ways of the atomic split-K, 1 = none): the kernel, and S > 1 when it writes S
@@ -132,7 +150,7 @@ static int launch_single(const GemmParams& p, const GemmKernel& k, int split, hi
     dim3 grid((p.N + k.tbn - 1) / k.tbn, (p.M + k.tbm - 1) / k.tbm, k.v == GemmVariant::dma || k.v == GemmVariant::reg ? split : 1);
     if (k.v == GemmVariant::pp) grid = dim3(std::min(grid.x * grid.y, 256u));      // persistent over the tile list: one workgroup per CU
     void* args[] = {const_cast<GemmParams*>(&p)};
-    return launch_kernel(k, grid, args, stream);
+    return launch_kernel(k, FAMILY_SINGLE, grid, args, stream);
 }
 // split-K into S fp32 slabs of the scratch (resolve_bf16 checked that they fit), then the reduce kernel applies the real epilogue
 static int launch_splitk(const GemmParams& p, const GemmKernel& k, int S, hipStream_t stream) {
@@ -145,7 +163,7 @@ static int launch_splitk(const GemmParams& p, const GemmKernel& k, int S, hipStr
     const unsigned blocks = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     long slab = q.slab;
     void* args[] = {const_cast<GemmParams*>(&p), &part, &slab};
-    return launch_kernel(splitk_reduce[S == 4], dim3(blocks), args, stream);
+    return launch_kernel(splitk_reduce[S == 4], FAMILY_SPLITK_REDUCE, dim3(blocks), args, stream);
 }
 static int launch_config(const GemmParams& p, const GemmConfig& c, int split, hipStream_t stream) {
     const GemmKernel* k;
@@ -593,7 +611,7 @@ static int launch_pair(GemmPair& g, const GemmConfig& c, hipStream_t stream) {
     }
     g.tiles0 = tiles[0];
     void* args[] = {&g};
-    return launch_kernel(*k, dim3(tiles[0] + tiles[1]), args, stream);
+    return launch_kernel(*k, FAMILY_PAIR, dim3(tiles[0] + tiles[1]), args, stream);
 }
 
 int launch_gemm_pair(const GemmParams& p0, const GemmParams& p1, int dtype, hipStream_t stream) {
@@ -607,6 +625,11 @@ int launch_gemm_pair(const GemmParams& p0, const GemmParams& p1, int dtype, hipS
     if (!ok) return separate();      // anything unusual
     GemmPair g;
     g.p[0] = p0; g.p[1] = p1;
+    if (g_pair_force) {              // tests: exactly this entry of the pair table, whatever the tune table holds
+        if (int rc = launch_pair(g, GemmConfig::decode(g_pair_force), stream)) return rc;
+        MEBT_HIP_CHECK(hipGetLastError());
+        return MEBT_OK;
+    }
     int choice = -1;
     {
         std::unique_lock<std::mutex> lk(g_tune_mutex);
@@ -656,7 +679,7 @@ static int launch_grouped(GroupedWgrad& c, const GemmConfig& cfg, hipStream_t st
     }
     for (int i = c.n; i <= MEBT_MAX_GROUP; ++i) c.tile_start[i] = tiles;
     void* args[] = {&c};
-    return launch_kernel(*k, dim3(tiles), args, stream);
+    return launch_kernel(*k, FAMILY_GROUPED, dim3(tiles), args, stream);
 }
 
 int launch_wgrad_grouped(GroupedWgrad& w, int dtype, hipStream_t stream) {

@@ -64,6 +64,11 @@ assert lib.mebt_model_create(C.byref(d), C.byref(h)) != 0
 assert lib.mebt_model_create(None, C.byref(h)) != 0
 # operator entry points: null pointers / bad shapes are rejected before anything is launched
 assert lib.mebt_op_gemm(_lib.BF16, None, None, None, None, None, None, 128, 128, 64, 64, 64, 128, 128, 1, 1, 0, 0, 0, 1, None) != 0
+assert lib.mebt_op_gemm_pair(*([None] * 14), 1, None) != 0
+two = lambda *v: (C.c_int32 * 2)(*v)
+nul = (C.c_void_p * 2)()
+assert lib.mebt_op_gemm_pair(nul, nul, nul, None, None, two(128, 128), two(128, 128), two(64, 64), two(64, 64), two(64, 64), two(128, 128),
+                             two(0, 0), two(0, 0), two(0, 0), 1, None) != 0 and b"null operand" in lib.mebt_last_error()
 assert lib.mebt_op_sample(None, None, 1.0, 0, 0.0, None, None, None, 4, 16384, None) != 0
 assert lib.mebt_op_topk_threshold(None, 5, None, None, 4, 16384, None) != 0
 print(f"asan host driver: {n_ok} model handles, {len(bad) + 2} rejected descriptors, no sanitizer finding")

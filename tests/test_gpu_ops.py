@@ -1,5 +1,6 @@
 """Operator-level parity of the HIP kernels (through the C ABI) against fp32/fp64 CPU references.
 GPU only.  fp32 mode must agree to ~1e-5 (exact-fp32 MFMA), bf16 mode to bf16 rounding."""
+import ctypes
 import math
 import numpy as np
 import pytest
@@ -29,21 +30,74 @@ def rnd(*shape, seed=0, scale=1.0, ints=False):
     return torch.randn(*shape, generator=g) * scale
 
 
-def run_gemm(dtype, A, B, M, N, K, a_kc, b_kc, bias=None, aux=None, epilogue=0, c_f32=0, beta=0, split_k=1, C0=None):
-    """A, B: CPU fp32 tensors already in their storage layout."""
+SENTINEL = -77.0     # exact in bf16 and fp32: what the padding of strided outputs and the guard row behind them are prefilled with
+POISON = 5.0         # the padding of strided inputs: a kernel that reads it computes a wrong integer
+
+
+def last_launch():
+    """(GEMM-family kernel launches since the previous call, the last of them) from mebt_debug_gemm_last_launch; family 0 single
+    product, 1 pair, 2 grouped, 3 split-K reduce, -1 none; `code` is the GemmConfig code byte of the kernel that really ran"""
+    out = (ctypes.c_int32 * 8)()
+    n = lib().mebt_debug_gemm_last_launch(out)
+    return n, dict(zip(("family", "code", "tbm", "tbn", "threads", "gx", "gy", "gz"), out))
+
+
+def assert_ran(tile, code, family=0, launches=1):
+    """the launches since the previous last_launch() were `launches` kernels, the last one the table entry (tile, code)"""
+    n, k = last_launch()
+    assert (n, k["family"], (k["tbm"], k["tbn"]), k["code"]) == (launches, family, tuple(tile), code), (n, k)
+    return k
+
+
+def strided(x, ld, t, off=0, fill=POISON):
+    """(keep-alive buffer, device pointer) of the rows of x at pitch `ld`, `off` elements behind a 16-byte aligned base; everything
+    around them holds `fill`"""
+    rows, cols = x.shape
+    flat = torch.full((off + (rows + 1) * ld + 8,), fill, device=DEV, dtype=t)
+    flat[off:off + rows * ld].view(rows, ld)[:, :cols] = x.to(DEV, t)
+    return flat, flat.data_ptr() + off * flat.element_size()
+
+
+class OutBuf:
+    """an [M, N] output at row pitch `ld`, `off` elements behind an aligned base, in a buffer prefilled with SENTINEL that also holds
+    a guard row behind the last row; the body starts as `init` (NaN: an element the kernel skipped is seen)"""
+
+    def __init__(self, M, N, ld, off, t, init=None):
+        self.M, self.N, self.ld, self.off = M, N, ld, off
+        self.flat = torch.full((off + (M + 1) * ld + 8,), SENTINEL, device=DEV, dtype=t)
+        self.body()[:] = float("nan") if init is None else init.to(DEV, t)
+        self.ptr = self.flat.data_ptr() + off * self.flat.element_size()
+
+    def body(self):
+        return self.flat[self.off:self.off + self.M * self.ld].view(self.M, self.ld)[:, :self.N]
+
+    def result(self):
+        """the body on the CPU as fp32, after asserting that nothing around it was written"""
+        out = self.body().float().cpu()
+        rest = self.flat.clone()
+        rest[self.off:self.off + self.M * self.ld].view(self.M, self.ld)[:, :self.N] = SENTINEL
+        assert bool((rest == SENTINEL).all()), "the kernel wrote outside its [M, N] output (padding columns / guard row)"
+        return out
+
+
+def run_gemm(dtype, A, B, M, N, K, a_kc, b_kc, bias=None, aux=None, epilogue=0, c_f32=0, beta=0, split_k=1, C0=None,
+             lda=None, ldb=None, ldc=None, ld_aux=None, c_off=0, c2_off=0, aux_off=0, C="alloc"):
+    """A, B: CPU fp32 tensors already in their storage layout.  lda / ldb / ldc / ld_aux: row pitches larger than the extent (inputs
+    padded with POISON, outputs with SENTINEL, which must survive); c_off / c2_off / aux_off: element offsets of C / C2 / aux from a
+    16-byte aligned base; C=None: no primary output (the inference form of the GELU product)."""
     t = tdt(dtype)
-    Ad, Bd = A.to(DEV, t).contiguous(), B.to(DEV, t).contiguous()
+    keepA, pA = strided(A, lda or A.shape[1], t)
+    keepB, pB = strided(B, ldb or B.shape[1], t)
     out_t = torch.float32 if (c_f32 or dtype == _lib.F32) else t
-    Cd = torch.full((M, N), float("nan"), device=DEV, dtype=out_t) if C0 is None else C0.to(DEV, out_t).clone()
-    C2d = torch.full((M, N), float("nan"), device=DEV, dtype=t) if epilogue == _lib.EPI_GELU else None
+    Cd = OutBuf(M, N, ldc or N, c_off, out_t, C0) if C is not None else None
+    C2d = OutBuf(M, N, ldc or N, c2_off, t) if epilogue == _lib.EPI_GELU else None
     bd = bias.to(DEV) if bias is not None else None
-    xd = aux.to(DEV, t).contiguous() if aux is not None else None
-    lda = A.shape[1]
-    ldb = B.shape[1]
-    check(lib().mebt_op_gemm(dtype, ptr(Ad), ptr(Bd), ptr(Cd), ptr(C2d), ptr(bd), ptr(xd), M, N, K, lda, ldb, N, N,
+    keepX, pX = strided(aux, ld_aux or N, t, aux_off) if aux is not None else (None, None)
+    check(lib().mebt_op_gemm(dtype, pA, pB, Cd.ptr if Cd else None, C2d.ptr if C2d else None, ptr(bd), pX, M, N, K,
+                             lda or A.shape[1], ldb or B.shape[1], ldc or N, ld_aux or N,
                              int(a_kc), int(b_kc), epilogue, c_f32, beta, split_k, cur_stream()))
     torch.cuda.synchronize()
-    return Cd.float().cpu(), (C2d.float().cpu() if C2d is not None else None)
+    return (Cd.result() if Cd else None), (C2d.result() if C2d is not None else None)
 
 
 def q(x, dtype):
@@ -66,6 +120,29 @@ def test_gemm_layouts_exact_integers(dtype, a_kc, b_kc, M, N, K):
     assert torch.equal(out.double(), ref), (out.double() - ref).abs().max()
 
 
+# What a forced (tile, variant) runs when the table of that tile has no such kernel, written from the header comment of
+# mebt_debug_gemm_variant and the fall-back rule of resolve_bf16 ("the LDS-DMA ring of the tile, as deep as the tile has"); every other
+# forced combination of these tests must run the very code it names.
+RESOLVES_TO = {
+    # register-staged exists for the four square-ish tiles only; a request without a ring gets the shallowest LDS-DMA ring
+    ((192, 128), 0): 2, ((96, 128), 0): 2, ((96, 64), 0): 2,
+    # the 256 x 256 tile is the 8-wave kernel (ring 2) under every code but 9: no register-staged, ring-1 or pipelined form of it
+    ((256, 256), 0): 2, ((256, 256), 1): 2, ((256, 256), 10): 2, ((256, 256), 11): 2, ((256, 256), 12): 2,
+    # two pipelines on 96 x 128 at ring 3 would need 168 KiB of LDS: the LDS-DMA ring 3 of the tile
+    ((96, 128), 19): 3,
+}
+RESOLVES_TO.update({(t, 1): 3 for t in [(128, 128), (128, 64), (64, 128), (64, 64), (192, 128), (96, 128), (96, 64)]})    # a forced ring 1 runs ring 3
+
+
+def expected_code(tile, variant):
+    return RESOLVES_TO.get((tuple(tile), variant), variant)
+
+
+def threads_of(tile, code):
+    """workgroup size of the table entry: 8 waves for the 256 x 256 kernels and the two-pipeline ones, 4 otherwise"""
+    return 512 if tuple(tile) == (256, 256) or 16 <= code < 32 else 256
+
+
 @pytest.mark.parametrize("staging", [0, 2, 1, 10, 11, 12])
 @pytest.mark.parametrize("tile", [(128, 128), (128, 64), (64, 128), (64, 64), (192, 128), (96, 128), (96, 64), (256, 256)])
 @pytest.mark.parametrize("a_kc,b_kc", [(1, 1), (1, 0), (0, 0), (0, 1)])
@@ -73,7 +150,8 @@ def test_gemm_every_tile_variant(tile, a_kc, b_kc, staging):
     """each block-tile x staging instantiation of the bf16 kernel (register-staged, LDS-DMA 2-stage,
     LDS-DMA 3-stage ring; 8 + ring: the software-pipelined main loop, rings 2-4), forced, on ragged integer operands.
     The 8-wave 256 x 256 tile has no pipelined variant: forced with one, it runs its own kernel (ring 2), which must
-    still be exact at the pipelined cases' K"""
+    still be exact at the pipelined cases' K.  The kernel that ran is the one the id names, or what RESOLVES_TO says: the ids
+    `0` of 192 x 128, 96 x 128 and 96 x 64 run the LDS-DMA ring 2, every id `1` runs ring 3, every 256 x 256 id the 8-wave kernel."""
     M, N, K = 328, 200, (320 if staging >= 8 else 192)
     Am, Bm = rnd(M, K, seed=11, ints=True), rnd(N, K, seed=12, ints=True)
     ref = Am.double() @ Bm.double().t()
@@ -81,11 +159,14 @@ def test_gemm_every_tile_variant(tile, a_kc, b_kc, staging):
     B = Bm if b_kc else Bm.t().contiguous()
     lib().mebt_debug_gemm_tile(*tile)
     lib().mebt_debug_gemm_variant(staging)
+    last_launch()
     try:
         out, _ = run_gemm(_lib.BF16, A, B, M, N, K, a_kc, b_kc, c_f32=1)
     finally:
         lib().mebt_debug_gemm_tile(0, 0)
         lib().mebt_debug_gemm_variant(-1)
+    k = assert_ran(tile, expected_code(tile, staging))
+    assert (k["threads"], k["gx"], k["gy"], k["gz"]) == (threads_of(tile, k["code"]), -(-N // tile[1]), -(-M // tile[0]), 1), k
     assert torch.equal(out.double(), ref), (out.double() - ref).abs().max()
 
 
@@ -99,11 +180,14 @@ def test_gemm_staggered_groups_256(M, N, K, b_kc):
     B = Bm if b_kc else Bm.t().contiguous()
     lib().mebt_debug_gemm_tile(256, 256)
     lib().mebt_debug_gemm_variant(9)
+    last_launch()
     try:
         out, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc, c_f32=1)
     finally:
         lib().mebt_debug_gemm_tile(0, 0)
         lib().mebt_debug_gemm_variant(-1)
+    k = assert_ran((256, 256), 9)
+    assert (k["threads"], k["gx"], k["gy"], k["gz"]) == (512, min(256, -(-M // 256) * -(-N // 256)), 1, 1), k      # persistent: one workgroup per tile, 256 at most
     assert torch.equal(out.double(), ref), (out.double() - ref).abs().max()
 
 
@@ -120,6 +204,7 @@ def test_gemm_staggered_groups_256_persistent_tile_loop(out, b_kc):
     bias = rnd(N, seed=53, ints=True) if "bias" in out else None
     lib().mebt_debug_gemm_tile(256, 256)
     lib().mebt_debug_gemm_variant(9)
+    last_launch()
     try:
         if out == "f32":
             got, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc, c_f32=1)
@@ -133,6 +218,8 @@ def test_gemm_staggered_groups_256_persistent_tile_loop(out, b_kc):
         else:
             got, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc)
             assert (got.double() - ref).abs().max() <= ref.abs().max() / 256 and torch.equal(got.double()[ref.abs() <= 256], ref[ref.abs() <= 256])
+        k = assert_ran((256, 256), 9)
+        assert (k["threads"], k["gx"], k["gy"], k["gz"]) == (512, 256, 1, 1), k      # more tiles than workgroups: the tile loop ran
     finally:
         lib().mebt_debug_gemm_tile(0, 0)
         lib().mebt_debug_gemm_variant(-1)
@@ -142,7 +229,8 @@ def test_gemm_staggered_groups_256_persistent_tile_loop(out, b_kc):
 @pytest.mark.parametrize("tile", [(96, 64), (64, 64), (96, 128), (64, 128), (128, 64)])
 @pytest.mark.parametrize("a_kc,b_kc", [(1, 1), (1, 0), (0, 0), (0, 1)])
 def test_gemm_two_pipeline_variants(tile, a_kc, b_kc, ring):
-    """8-wave workgroups running two 4-wave pipelines on alternate k-tiles (variant 16 + ring depth), ragged M / N"""
+    """8-wave workgroups running two 4-wave pipelines on alternate k-tiles (variant 16 + ring depth), ragged M / N.  The
+    cases of 96 x 128 at ring 3 name a kernel that never runs: its two rings (168 KiB) exceed the LDS, the LDS-DMA ring 3 runs instead."""
     M, N, K = 328, 200, 512
     Am, Bm = rnd(M, K, seed=21, ints=True), rnd(N, K, seed=22, ints=True)
     ref = Am.double() @ Bm.double().t()
@@ -150,11 +238,14 @@ def test_gemm_two_pipeline_variants(tile, a_kc, b_kc, ring):
     B = Bm if b_kc else Bm.t().contiguous()
     lib().mebt_debug_gemm_tile(*tile)
     lib().mebt_debug_gemm_variant(16 + ring)
+    last_launch()
     try:
         out, _ = run_gemm(_lib.BF16, A, B, M, N, K, a_kc, b_kc, c_f32=1)
     finally:
         lib().mebt_debug_gemm_tile(0, 0)
         lib().mebt_debug_gemm_variant(-1)
+    k = assert_ran(tile, expected_code(tile, 16 + ring))
+    assert k["threads"] == threads_of(tile, k["code"]), k
     assert torch.equal(out.double(), ref), (out.double() - ref).abs().max()
 
 
@@ -173,25 +264,37 @@ def test_gemm_ragged_reduction_and_splitk(dtype):
     assert torch.equal(out.double(), ref + C0.double())
 
 
-@pytest.mark.parametrize("dtype,tol", [(_lib.BF16, 2e-2), (_lib.F32, 2e-5)])
-def test_gemm_epilogues(dtype, tol):
-    M, N, K = 192, 256, 128
+def check_four_epilogues(dtype, tol, M, N, K, **pitch):
     A, B = q(rnd(M, K, seed=6), dtype), q(rnd(N, K, seed=7, scale=0.1), dtype)
     bias = rnd(N, seed=8)
     aux = q(rnd(M, N, seed=9), dtype)
     lin = A.double() @ B.double().t() + bias.double()
-    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias)
+    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias, **pitch)
     assert (out.double() - lin).abs().max() < tol * max(1, lin.abs().max())
-    out, g = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias, epilogue=_lib.EPI_GELU)
+    out, g = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias, epilogue=_lib.EPI_GELU, **pitch)
     assert (out.double() - lin).abs().max() < tol * max(1, lin.abs().max())
     assert (g.double() - F.gelu(lin)).abs().max() < tol * max(1, lin.abs().max())
-    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias, aux=aux, epilogue=_lib.EPI_RESID)
+    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, bias=bias, aux=aux, epilogue=_lib.EPI_RESID, **pitch)
     assert (out.double() - (lin + aux.double())).abs().max() < tol * max(1, lin.abs().max())
     x = aux.double().requires_grad_(True)
     F.gelu(x).sum().backward()
     nob = A.double() @ B.double().t()
-    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, aux=aux, epilogue=_lib.EPI_GELU_BWD)
+    out, _ = run_gemm(dtype, A, B, M, N, K, 1, 1, aux=aux, epilogue=_lib.EPI_GELU_BWD, **pitch)
     assert (out.double() - nob * x.grad).abs().max() < tol * max(1, nob.abs().max())
+
+
+@pytest.mark.parametrize("dtype,tol", [(_lib.BF16, 2e-2), (_lib.F32, 2e-5)])
+def test_gemm_epilogues(dtype, tol):
+    check_four_epilogues(dtype, tol, 192, 256, 128)
+
+
+def test_gemm_f32_epilogues_ragged_and_strided():
+    """the fp32 parity kernels' direct epilogue at an output ragged against every fp32 tile (200 x 204, N % 8 == 4, K = 80 = 5 k-tiles)
+    with C, C2 and aux at a row pitch of N + 4: the same four epilogues and the same tolerance as test_gemm_epilogues"""
+    N = 204
+    check_four_epilogues(_lib.F32, 2e-5, 200, N, 80, ldc=N + 4, ld_aux=N + 4)
+    n, k = last_launch()
+    assert (k["family"], k["code"], k["threads"]) == (0, 0, 256), k
 
 
 @pytest.mark.parametrize("variant", [34, 67])
@@ -211,14 +314,19 @@ def test_gemm_splitk_slabs_with_epilogues(tile, variant, b_kc):
     lib().mebt_debug_gemm_scratch(ptr(scratch), scratch.numel())
     lib().mebt_debug_gemm_tile(*tile)
     lib().mebt_debug_gemm_variant(variant)
+    reduce_code = variant & ~7                 # the reduce kernel of 2 (32) or 4 (64) slabs: launched last, after the slab-writing GEMM
+    last_launch()
     try:
         out, _ = run_gemm(_lib.BF16, A, B, M, N, K, 1, b_kc, bias=bias)
+        assert_ran((0, 0), reduce_code, family=3, launches=2)
         assert (out.double() - lin).abs().max() < tol * max(1, lin.abs().max())
         assert scratch[384 << 20:(384 << 20) + 4 * M * N].view(torch.float32).abs().sum().item() > 0     # the slabs were really used
         out, g = run_gemm(_lib.BF16, A, B, M, N, K, 1, b_kc, bias=bias, epilogue=_lib.EPI_GELU)
+        assert_ran((0, 0), reduce_code, family=3, launches=2)
         assert (out.double() - lin).abs().max() < tol * max(1, lin.abs().max())
         assert (g.double() - F.gelu(lin)).abs().max() < tol * max(1, lin.abs().max())
         out, _ = run_gemm(_lib.BF16, A, B, M, N, K, 1, b_kc, bias=bias, aux=aux, epilogue=_lib.EPI_RESID)
+        assert_ran((0, 0), reduce_code, family=3, launches=2)
         assert (out.double() - (lin + aux.double())).abs().max() < tol * max(1, lin.abs().max())
     finally:
         lib().mebt_debug_gemm_tile(0, 0)
@@ -247,6 +355,145 @@ def test_gemm_forced_tile_without_kernel_is_rejected():
     torch.cuda.synchronize()
     assert st == MEBT_STATUS_EINVAL and b"256 x 128" in lib().mebt_last_error()
     assert torch.all(Cd == 7.0)
+
+
+def gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def gelu_grad64(x):
+    return 0.5 * (1.0 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
+
+
+def assert_cheap_erf_bound(got, ref, arg, what):
+    """per element |got - ref| <= 2^-7 |ref| + 3e-4 |arg|: one bf16 ulp of the result (its rounding, and a rounding flipped by the
+    approximation) plus the documented bound of the bf16 epilogues' cheap erf (common.h: |error| <= 5e-4, which enters both gelu(x) and
+    acc * gelu'(x) times 0.5 |arg|) with 20 % margin"""
+    err, bound = (got.double() - ref).abs(), ref.abs() / 128 + 3e-4 * arg.abs()
+    worst = (err - bound).max().item()
+    print(f"{what}: max |err| {err.max().item():.3e}, max (err - bound) {worst:.3e}, max err / bound {(err / bound.clamp_min(1e-30)).max().item():.3f}")
+    assert worst <= 0, (what, worst)
+
+
+def bf16_round(x):
+    return x.to(torch.bfloat16).double()
+
+
+_edge_operands = {}
+
+
+def edge_operands(N):
+    """integer operands, their fp64 product, an integer bias and an integer aux at M = 328, K = 128, computed once per N"""
+    if N not in _edge_operands:
+        M, K = 328, 128
+        Am, Bm = rnd(M, K, seed=61, ints=True), rnd(N, K, seed=62, ints=True)
+        _edge_operands[N] = (Am, Bm, Am.double() @ Bm.double().t(), rnd(N, seed=63, ints=True), rnd(M, N, seed=64, ints=True))
+    return _edge_operands[N]
+
+
+EDGE_KERNELS = [((128, 128), 0), ((96, 64), 3), ((192, 128), 8 + 3), ((128, 64), 16 + 2), ((256, 256), 2), ((256, 256), 9)]
+EDGE_EPILOGUES = ["bias", "gelu", "gelu_no_c", "resid", "gelu_bwd"]
+
+
+def run_edge_epilogue(epi, N, b_kc, **kw):
+    """one epilogue of the bf16 kernels on the edge operands, checked: the linear part and the residual sum exactly (integers, one
+    bf16 rounding), the two GELU forms to assert_cheap_erf_bound"""
+    M, K = 328, 128
+    Am, Bm, acc, bias, aux = edge_operands(N)
+    B = Bm if b_kc else Bm.t().contiguous()
+    if epi == "bias":
+        out, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc, bias=bias, **kw)
+        assert torch.equal(out.double(), bf16_round(acc + bias.double()))
+    elif epi in ("gelu", "gelu_no_c"):
+        # A * 0.25 is exact in bf16 and spreads the pre-activations over about +-10: both tails and the middle of the erf
+        pre = acc * 0.25 + bias.double()
+        out, g = run_gemm(_lib.BF16, Am * 0.25, B, M, N, K, 1, b_kc, bias=bias, epilogue=_lib.EPI_GELU, C=("alloc" if epi == "gelu" else None), **kw)
+        assert (out is None) == (epi == "gelu_no_c")
+        if out is not None:
+            assert torch.equal(out.double(), bf16_round(pre))
+        assert_cheap_erf_bound(g, gelu64(pre), pre, epi)
+    elif epi == "resid":
+        out, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc, bias=bias, aux=aux, epilogue=_lib.EPI_RESID, **kw)
+        assert torch.equal(out.double(), bf16_round(acc + bias.double() + aux.double()))
+    else:
+        out, _ = run_gemm(_lib.BF16, Am, B, M, N, K, 1, b_kc, aux=aux, epilogue=_lib.EPI_GELU_BWD, **kw)
+        assert_cheap_erf_bound(out, acc * gelu_grad64(aux.double()), acc, epi)
+
+
+@pytest.mark.parametrize("N", [200, 204])
+@pytest.mark.parametrize("epi", EDGE_EPILOGUES)
+@pytest.mark.parametrize("b_kc", [1, 0])
+@pytest.mark.parametrize("tile,variant", EDGE_KERNELS)
+def test_gemm_epilogue_of_every_kernel_family_ragged(tile, variant, b_kc, epi, N):
+    """every epilogue implementation (the direct store of the register-staged kernel, the LDS-staged one of the LDS-DMA / pipelined
+    kernels, the two-pipeline merge, the 8-wave kernel, the swizzled slab of the persistent 256 x 256 kernel) x every epilogue, bf16
+    store, on an output ragged against every tile (328 x 200) and with N % 8 == 4 (328 x 204: the last lane of a row stores one
+    4-column half).  A row-contiguous B needs N % 8 == 0: N = 204 with b_kc = 0 is rejected with MEBT_STATUS_ESHAPE before any launch."""
+    lib().mebt_debug_gemm_tile(*tile)
+    lib().mebt_debug_gemm_variant(variant)
+    last_launch()
+    try:
+        if not b_kc and N % 8:
+            with pytest.raises(_lib.MebtError, match="status 2: gemm: row extent of an RC operand must be a multiple of 8"):
+                run_edge_epilogue(epi, N, b_kc)
+            assert last_launch()[0] == 0
+            return
+        run_edge_epilogue(epi, N, b_kc)
+    finally:
+        lib().mebt_debug_gemm_tile(0, 0)
+        lib().mebt_debug_gemm_variant(-1)
+    k = assert_ran(tile, variant)
+    assert k["threads"] == threads_of(tile, variant), k
+
+
+NARROW_CAUSES = {      # what makes epilogue_via_lds leave its 16-byte path: one cause at a time, then all of them
+    "n204": dict(N=204), "ldc": dict(ldc=4), "ld_aux": dict(ld_aux=4), "c_off": dict(c_off=4), "c2_off": dict(c2_off=4), "aux_off": dict(aux_off=4),
+    "all": dict(N=204, ldc=4, ld_aux=4, c_off=4, c2_off=4, aux_off=4),
+}
+
+
+@pytest.mark.parametrize("cause,epi", [(c, e) for c in NARROW_CAUSES for e in ("resid", "gelu")
+                                       if not (c == "c2_off" and e == "resid") and not (c == "aux_off" and e == "gelu")])
+@pytest.mark.parametrize("tile,variant", [((128, 128), 3), ((96, 64), 8 + 2)])
+def test_gemm_epilogue_narrow_store_paths(tile, variant, cause, epi):
+    """the 8-byte branches of the LDS-staged epilogue: N % 8 == 4, a row pitch of C / C2 or of aux that is no multiple of 8 (N + 4),
+    and C, C2 or aux 8 bytes off a 16-byte boundary.  Outputs sit in SENTINEL-filled buffers (padding columns, guard row), aux in a
+    POISON-filled one; exactness as in the ragged test above."""
+    kw = dict(NARROW_CAUSES[cause])
+    N = kw.pop("N", 200)
+    if "ldc" in kw:
+        kw["ldc"] = N + 4
+    if "ld_aux" in kw:
+        kw["ld_aux"] = N + 4
+    if epi == "gelu":
+        kw.pop("aux_off", None)
+    else:
+        kw.pop("c2_off", None)
+    lib().mebt_debug_gemm_tile(*tile)
+    lib().mebt_debug_gemm_variant(variant)
+    last_launch()
+    try:
+        run_edge_epilogue(epi, N, 1, **kw)
+    finally:
+        lib().mebt_debug_gemm_tile(0, 0)
+        lib().mebt_debug_gemm_variant(-1)
+    assert_ran(tile, variant)
+
+
+@pytest.mark.parametrize("dtype", [_lib.BF16, _lib.F32])
+@pytest.mark.parametrize("a_kc,b_kc", [(1, 1), (1, 0), (0, 0), (0, 1)])
+def test_gemm_strided_operands_exact_integers(dtype, a_kc, b_kc):
+    """operands that are column blocks of wider buffers, as the engine passes them (the dgrad of the k|v projection reads A at
+    lda = 2 d): a k-contiguous operand at a pitch of K + 64, a row-contiguous one at its row count + 8, the padding filled with
+    POISON; exact on integers"""
+    M, N, K = 200, 136, 128
+    Am, Bm = rnd(M, K, seed=1, ints=True), rnd(N, K, seed=2, ints=True)
+    ref = Am.double() @ Bm.double().t()
+    A = Am if a_kc else Am.t().contiguous()
+    B = Bm if b_kc else Bm.t().contiguous()
+    out, _ = run_gemm(dtype, A, B, M, N, K, a_kc, b_kc, c_f32=1, lda=(K + 64 if a_kc else M + 8), ldb=(K + 64 if b_kc else N + 8))
+    assert torch.equal(out.double(), ref), (out.double() - ref).abs().max()
+
 
 @pytest.mark.parametrize("dtype,tol", [(_lib.BF16, 2e-2), (_lib.F32, 1e-5)])
 @pytest.mark.parametrize("rows,d", [(37, 64), (130, 256), (64, 1024), (5, 320)])
