@@ -338,6 +338,13 @@ int mebt_op_cast_f16(const float* src, void* dst, int64_t n, mebt_stream_t strea
 int mebt_op_frames_to_video(const uint8_t* frames, float* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
                             int32_t S, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const float* lut,
                             const int32_t* slots, int32_t Bout, mebt_stream_t stream);
+/* The same crop and resize with uint8 output for the real side of FVD / KVD (reference measure_fvd_with_numpy.py:63): the resampled
+ * byte goes through the uint8 table `lut` [256] = ((float32(u) / 255 - 0.5 + 0.5) * 255).byte() (mebt_amd/frames.py:byte_table; not
+ * the identity) -> out [Bout, T, R, R, 3] uint8, the clip layout of mebt_op_i3d_preprocess.  Every other argument as above.  No
+ * floating point at all: the result equals the reference's bytes. */
+int mebt_op_frames_to_clip_u8(const uint8_t* frames, uint8_t* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
+                              int32_t S, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const uint8_t* lut,
+                              const int32_t* slots, int32_t Bout, mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

@@ -10,6 +10,14 @@
 // One workgroup per (frame, tile of `rows` output rows): the horizontal pass resamples the source rows the tile needs
 // [xmin[r0], xmin[r1] + n[r1]) into LDS as uint8, the vertical pass reads them back and stores one fp32 plane per channel, lanes
 // along W.  Same-size frames (crop side == R) take a second kernel: crop + normalise + HWC -> CHW transpose.
+//
+// Both kernels are templates on the output element.  float: the clip above.  uint8_t (`mebt_op_frames_to_clip_u8`, the real side of
+// FVD): the resampled byte goes through a 256-entry uint8 table instead (the reference's `((video + 0.5) * 255).byte()`, built on the
+// host: mebt_amd/frames.py:byte_table) and is stored as the I3D path's clip [B, T, R, R, 3].  There a frame is R rows of R * 3 bytes
+// and a channel is just a column, so the vertical pass walks the tile's contiguous run of output bytes four at a time, from the
+// first dword boundary at or below the run's start: one dword store per lane, byte stores only at the two ragged ends.
+#include <string>
+
 #include "../common.h"
 #include "../../../include/mebt_hip.h"
 
@@ -23,12 +31,23 @@ __device__ __forceinline__ int clip8(int acc) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-__global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t* __restrict__ frames, float* __restrict__ out, int T,
+// the bytes of `v` (lowest first) belong at run[j, j + 4), of which [0, n) exists; run + j is dword aligned
+__device__ __forceinline__ void store_quad(uint8_t* run, int j, int n, uint32_t v) {
+    if (j >= 0 && j + 4 <= n) {
+        *reinterpret_cast<uint32_t*>(run + j) = v;
+        return;
+    }
+    for (int c = 0; c < 4; ++c)
+        if (j + c >= 0 && j + c < n) run[j + c] = (uint8_t)(v >> (8 * c));
+}
+
+template <typename Out>
+__global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t* __restrict__ frames, Out* __restrict__ out, int T,
                                                                    int Hs, int Ws, int y0, int x0, int R, const int32_t* __restrict__ tab,
-                                                                   int K, int rows, int span, const float* __restrict__ lut,
+                                                                   int K, int rows, int span, const Out* __restrict__ lut,
                                                                    const int32_t* __restrict__ slots, int Bout) {
     extern __shared__ uint8_t tmp[];          // [span][R][3] uint8: the horizontally resampled source rows
-    __shared__ float lut_s[256];
+    __shared__ Out lut_s[256];
     const int n = blockIdx.y, bl = n / T, t = n - bl * T;
     const int b = slots ? slots[bl] : bl;
     if (b < 0 || b >= Bout) return;           // uniform over the block
@@ -63,9 +82,51 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t
     }
     __syncthreads();
 
-    // vertical pass: output rows [r0, r1] from tmp, then the normalisation table; lanes along W -> coalesced plane stores
     const size_t plane = (size_t)R * R;
-    float* o = out + ((size_t)b * 3 * T + t) * plane;            // channel c at o + c * T * plane
+    if constexpr (sizeof(Out) == 1) {
+        // vertical pass over the tile's run of (r1 - r0 + 1) * R3 output bytes, then the byte table
+        uint8_t* run = out + (((size_t)b * T + t) * R + r0) * R3;
+        const int nrun = (r1 - r0 + 1) * R3;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
+        for (int j = 4 * (int)threadIdx.x - mis; j < nrun; j += 4 * FR_THREADS) {
+            const int rr = max(j, 0) / R3, col = max(j, 0) - rr * R3;
+            uint32_t v = 0;
+            if (j >= 0 && j + 4 <= nrun && col + 4 <= R3) {       // four columns of one output row: one walk over its taps
+                const int r = r0 + rr;
+                const int ym = xmin[r] - ybase;
+                const int m = min(cnt[r], nrow - ym);
+                const int32_t* w = kk + (size_t)r * K;
+                const uint8_t* s = tmp + ym * R3 + col;
+                int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21, a3 = 1 << 21;
+                for (int k = 0; k < m; ++k) {
+                    const int wk = w[k];
+                    a0 += wk * (int)s[k * R3];
+                    a1 += wk * (int)s[k * R3 + 1];
+                    a2 += wk * (int)s[k * R3 + 2];
+                    a3 += wk * (int)s[k * R3 + 3];
+                }
+                v = (uint32_t)lut_s[clip8(a0)] | (uint32_t)lut_s[clip8(a1)] << 8 | (uint32_t)lut_s[clip8(a2)] << 16 |
+                    (uint32_t)lut_s[clip8(a3)] << 24;
+            } else {                                              // a row boundary or a ragged end of the run: byte by byte
+                for (int c = 0; c < 4; ++c) {
+                    const int jj = j + c;
+                    if (jj < 0 || jj >= nrun) continue;
+                    const int r = r0 + jj / R3, cc = jj % R3;
+                    const int ym = xmin[r] - ybase;
+                    const int m = min(cnt[r], nrow - ym);
+                    const int32_t* w = kk + (size_t)r * K;
+                    const uint8_t* s = tmp + ym * R3 + cc;
+                    int a = 1 << 21;
+                    for (int k = 0; k < m; ++k) a += w[k] * (int)s[k * R3];
+                    v |= (uint32_t)lut_s[clip8(a)] << (8 * c);
+                }
+            }
+            store_quad(run, j, nrun, v);
+        }
+        return;
+    }
+    // vertical pass: output rows [r0, r1] from tmp, then the normalisation table; lanes along W -> coalesced plane stores
+    Out* o = out + ((size_t)b * 3 * T + t) * plane;              // channel c at o + c * T * plane
     const int nout = (r1 - r0 + 1) * R;
     for (int i = threadIdx.x; i < nout; i += FR_THREADS) {
         const int rr = i / R, x = i - rr * R, r = r0 + rr;
@@ -88,10 +149,11 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t
 }
 
 // crop side == R: no resampling (PIL's same-size resize is a copy)
-__global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* __restrict__ frames, float* __restrict__ out, int T, int Hs,
-                                                                 int Ws, int y0, int x0, int R, const float* __restrict__ lut,
+template <typename Out>
+__global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* __restrict__ frames, Out* __restrict__ out, int T, int Hs,
+                                                                 int Ws, int y0, int x0, int R, const Out* __restrict__ lut,
                                                                  const int32_t* __restrict__ slots, int Bout) {
-    __shared__ float lut_s[256];
+    __shared__ Out lut_s[256];
     const int n = blockIdx.y, bl = n / T, t = n - bl * T;
     const int b = slots ? slots[bl] : bl;
     if (b < 0 || b >= Bout) return;
@@ -99,7 +161,24 @@ __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* 
     __syncthreads();
     const size_t plane = (size_t)R * R;
     const uint8_t* src = frames + (size_t)n * Hs * Ws * 3;
-    float* o = out + ((size_t)b * 3 * T + t) * plane;
+    if constexpr (sizeof(Out) == 1) {
+        // the frame is one run of R rows of R3 bytes; source row y is the R3 bytes at src + ((y0 + y) * Ws + x0) * 3
+        const int R3 = R * 3, nrun = R * R3;
+        uint8_t* run = out + ((size_t)b * T + t) * nrun;
+        const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
+        for (int j = 4 * (int)(blockIdx.x * FR_THREADS + threadIdx.x) - mis; j < nrun; j += 4 * (int)gridDim.x * FR_THREADS) {
+            uint32_t v = 0;
+            for (int c = 0; c < 4; ++c) {
+                const int jj = j + c;
+                if (jj < 0 || jj >= nrun) continue;
+                const int y = jj / R3, col = jj - y * R3;
+                v |= (uint32_t)lut_s[src[((size_t)(y0 + y) * Ws + x0) * 3 + col]] << (8 * c);
+            }
+            store_quad(run, j, nrun, v);
+        }
+        return;
+    }
+    Out* o = out + ((size_t)b * 3 * T + t) * plane;
     for (int i = blockIdx.x * FR_THREADS + threadIdx.x; i < R * R; i += gridDim.x * FR_THREADS) {
         const int y = i / R, x = i - y * R;
         const uint8_t* p = src + ((size_t)(y0 + y) * Ws + x0 + x) * 3;
@@ -111,28 +190,49 @@ __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* 
 
 hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+int fail(const char* who, const char* what) {
+    mebt_set_error((std::string(who) + ": " + what).c_str());
+    return MEBT_EINVAL;
+}
+
+// argument checks and launch of both entries
+template <typename Out>
+int frames_launch(const char* who, const uint8_t* frames, Out* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
+                  int32_t S_, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const Out* lut, const int32_t* slots,
+                  int32_t Bout, mebt_stream_t stream) {
+    if (!frames || !out || !lut) return fail(who, "null pointer");
+    if (N < 1 || T < 1 || N % T || Hs < 1 || Ws < 1 || R < 1 || Bout < 1) return fail(who, "bad shape");
+    if (S_ < 1 || y0 < 0 || x0 < 0 || y0 + S_ > Hs || x0 + S_ > Ws) return fail(who, "crop box outside the frame");
+    if (!slots && N / T > Bout) return fail(who, "more clips than output slots");
+    // uint8 output: the frame's R * R * 3 bytes are indexed in int
+    if ((long)Hs * Ws * 3 > (1l << 40) || (long)R * R * (sizeof(Out) == 1 ? 3 : 1) > (1l << 30)) return fail(who, "frame too large");
+    if (N > 65535) return fail(who, "at most 65535 frames per launch");
+    if (S_ == R) {
+        const long work = sizeof(Out) == 1 ? ((long)R * R * 3 + 3) / 4 + 1 : (long)R * R;      // lanes per frame: dwords of the run, or pixels
+        const int g = (int)((work + FR_THREADS - 1) / FR_THREADS);
+        hipLaunchKernelGGL(frames_copy_kernel<Out>, dim3(g < 64 ? g : 64, N), dim3(FR_THREADS), 0, S(stream), frames, out, T, Hs, Ws, y0, x0, R,
+                           lut, slots, Bout);
+    } else {
+        if (!tab || K < 1 || rows < 1 || span < 1 || span > S_) return fail(who, "bad coefficient table");
+        const long lds = (long)span * R * 3;
+        if (lds > FR_MAX_LDS) return fail(who, "the source rows of one tile exceed the LDS");
+        hipLaunchKernelGGL(frames_resize_kernel<Out>, dim3((R + rows - 1) / rows, N), dim3(FR_THREADS), (size_t)lds, S(stream), frames, out, T,
+                           Hs, Ws, y0, x0, R, tab, K, rows, span, lut, slots, Bout);
+    }
+    MEBT_HIP_CHECK(hipGetLastError());
+    return MEBT_OK;
+}
+
 }  // namespace
 
 extern "C" int mebt_op_frames_to_video(const uint8_t* frames, float* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
                                        int32_t S_, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const float* lut,
                                        const int32_t* slots, int32_t Bout, mebt_stream_t stream) {
-    if (!frames || !out || !lut) { mebt_set_error("frames_to_video: null pointer"); return MEBT_EINVAL; }
-    if (N < 1 || T < 1 || N % T || Hs < 1 || Ws < 1 || R < 1 || Bout < 1) { mebt_set_error("frames_to_video: bad shape"); return MEBT_EINVAL; }
-    if (S_ < 1 || y0 < 0 || x0 < 0 || y0 + S_ > Hs || x0 + S_ > Ws) { mebt_set_error("frames_to_video: crop box outside the frame"); return MEBT_EINVAL; }
-    if (!slots && N / T > Bout) { mebt_set_error("frames_to_video: more clips than output slots"); return MEBT_EINVAL; }
-    if ((long)Hs * Ws * 3 > (1l << 40) || (long)R * R > (1l << 30)) { mebt_set_error("frames_to_video: frame too large"); return MEBT_EINVAL; }
-    if (N > 65535) { mebt_set_error("frames_to_video: at most 65535 frames per launch"); return MEBT_EINVAL; }
-    if (S_ == R) {
-        const int g = (int)((R * R + FR_THREADS - 1) / FR_THREADS);
-        hipLaunchKernelGGL(frames_copy_kernel, dim3(g < 64 ? g : 64, N), dim3(FR_THREADS), 0, S(stream), frames, out, T, Hs, Ws, y0, x0, R, lut,
-                           slots, Bout);
-    } else {
-        if (!tab || K < 1 || rows < 1 || span < 1 || span > S_) { mebt_set_error("frames_to_video: bad coefficient table"); return MEBT_EINVAL; }
-        const long lds = (long)span * R * 3;
-        if (lds > FR_MAX_LDS) { mebt_set_error("frames_to_video: the source rows of one tile exceed the LDS"); return MEBT_EINVAL; }
-        hipLaunchKernelGGL(frames_resize_kernel, dim3((R + rows - 1) / rows, N), dim3(FR_THREADS), (size_t)lds, S(stream), frames, out, T, Hs, Ws,
-                           y0, x0, R, tab, K, rows, span, lut, slots, Bout);
-    }
-    MEBT_HIP_CHECK(hipGetLastError());
-    return MEBT_OK;
+    return frames_launch<float>("frames_to_video", frames, out, N, T, Hs, Ws, y0, x0, S_, R, tab, K, rows, span, lut, slots, Bout, stream);
+}
+
+extern "C" int mebt_op_frames_to_clip_u8(const uint8_t* frames, uint8_t* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0,
+                                         int32_t x0, int32_t S_, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span,
+                                         const uint8_t* lut, const int32_t* slots, int32_t Bout, mebt_stream_t stream) {
+    return frames_launch<uint8_t>("frames_to_clip_u8", frames, out, N, T, Hs, Ws, y0, x0, S_, R, tab, K, rows, span, lut, slots, Bout, stream);
 }

@@ -17,6 +17,11 @@ as Pillow does and the kernel only multiplies and adds int32:
 A same-size resize is a copy (the tables degenerate to one weight of 2**22).  The crop is square, so one table serves both
 axes.  `resize_twin` is the numpy statement of the same algorithm: the documented definition the tests hold the tables to
 (against PIL) and the kernel to; the product never computes frames on the CPU.
+
+The real side of FVD / KVD wants the same clips as bytes: the reference turns the loader's float clip back into uint8 with
+`((video + 0.5) * 255).byte()` (measure_fvd_with_numpy.py:63), which truncates and so moves some levels down by one.
+`frames_to_clip_u8` (`mebt_op_frames_to_clip_u8`) is the same kernel with that 256-entry byte table (`byte_table`) in place of the
+float one and the I3D path's clip layout [B, T, R, R, 3] as output; `clip_u8_twin` is its numpy statement.
 """
 import math
 
@@ -76,6 +81,12 @@ def norm_table():
     return t - 0.5
 
 
+def byte_table():
+    """uint8 -> uint8 as the reference's FVD script turns the loader's float clip back into bytes: its own expression, on CPU
+    torch.  Not the identity: float32(u) / 255 - 0.5 + 0.5 can land below u / 255 and `.byte()` truncates."""
+    return ((torch.from_numpy(norm_table()) + 0.5) * 255).byte().numpy()
+
+
 def _pass(src, xmin, cnt, k, axis):
     """one Pillow pass along `axis` of an [H, W, C] uint8 image"""
     src = np.moveaxis(src, axis, 0).astype(np.int64)
@@ -105,6 +116,13 @@ def clip_twin(frames, R):
     lut = norm_table()
     out = [lut[resize_twin(np.ascontiguousarray(f[y0:y0 + S, x0:x0 + S]), R)] for f in frames]
     return np.stack(out).transpose(3, 0, 1, 2)
+
+
+def clip_u8_twin(frames, R):
+    """numpy twin of the uint8 ingest of one clip: uint8 [T, Hs, Ws, 3] -> uint8 [T, R, R, 3] (tests only)"""
+    y0, x0, S = crop_box(frames.shape[1], frames.shape[2])
+    lut = byte_table()
+    return np.stack([lut[resize_twin(np.ascontiguousarray(f[y0:y0 + S, x0:x0 + S]), R)] for f in frames])
 
 
 # ---- device side ---------------------------------------------------------------------------------------------------------
@@ -137,6 +155,7 @@ class _Plan:
             tab = np.zeros(1, np.int32)
         self.tab = torch.from_numpy(tab).to(device)
         self.lut = torch.from_numpy(norm_table()).to(device)
+        self.byte_lut = torch.from_numpy(byte_table()).to(device)
 
 
 def plan(Hs, Ws, R, device):
@@ -147,9 +166,8 @@ def plan(Hs, Ws, R, device):
     return p
 
 
-def frames_to_video(frames, R, out=None, slots=None):
-    """uint8 frames [B, T, Hs, Ws, 3] on the GPU -> the reference's float32 clip [B, 3, T, R, R].  With `out`
-    [Bout, 3, T, R, R] and `slots` (int32 [B] on the device), clip i is written to out[slots[i]] (mixed-size batches)."""
+def _ingest(frames, R, out, slots, u8):
+    """argument checks and launch of both outputs: float32 [B, 3, T, R, R], or (u8) uint8 [B, T, R, R, 3]"""
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
         raise ValueError(f"frame ingest: expected uint8 [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_cuda:
@@ -157,13 +175,15 @@ def frames_to_video(frames, R, out=None, slots=None):
     frames = frames.contiguous()
     B, T, Hs, Ws, _ = frames.shape
     p = plan(Hs, Ws, R, frames.device)
+    dtype, shape = (torch.uint8, (T, R, R, 3)) if u8 else (torch.float32, (3, T, R, R))
     if out is None:
         if slots is not None:
             raise ValueError("frame ingest: `slots` needs `out`")
-        out = torch.empty(B, 3, T, R, R, device=frames.device, dtype=torch.float32)
+        out = torch.empty(B, *shape, device=frames.device, dtype=dtype)
     else:
-        if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape[1:]) != (3, T, R, R):
-            raise ValueError(f"frame ingest: `out` must be contiguous float32 [*, 3, {T}, {R}, {R}], got {tuple(out.shape)}")
+        if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape[1:]) != shape:
+            raise ValueError(f"frame ingest: `out` must be contiguous {str(dtype).split('.')[-1]} [*, {', '.join(map(str, shape))}], "
+                             f"got {tuple(out.shape)}")
         if slots is None and out.shape[0] != B:
             raise ValueError("frame ingest: `out` has another batch size and no `slots` were given")
     if slots is not None:
@@ -171,15 +191,29 @@ def frames_to_video(frames, R, out=None, slots=None):
             raise ValueError("frame ingest: `slots` must be int32 [B] on the frames' device")
     if B == 0:
         return out
-    _lib.check(_lib.load().mebt_op_frames_to_video(
+    lib = _lib.load()
+    _lib.check((lib.mebt_op_frames_to_clip_u8 if u8 else lib.mebt_op_frames_to_video)(
         _lib.ptr(frames), _lib.ptr(out), B * T, T, Hs, Ws, p.y0, p.x0, p.S, R, _lib.ptr(p.tab), p.K, p.rows, p.span,
-        _lib.ptr(p.lut), _lib.ptr(slots), int(out.shape[0]), _lib.cur_stream()))
+        _lib.ptr(p.byte_lut if u8 else p.lut), _lib.ptr(slots), int(out.shape[0]), _lib.cur_stream()))
     return out
+
+
+def frames_to_video(frames, R, out=None, slots=None):
+    """uint8 frames [B, T, Hs, Ws, 3] on the GPU -> the reference's float32 clip [B, 3, T, R, R].  With `out`
+    [Bout, 3, T, R, R] and `slots` (int32 [B] on the device), clip i is written to out[slots[i]] (mixed-size batches)."""
+    return _ingest(frames, R, out, slots, u8=False)
+
+
+def frames_to_clip_u8(frames, R, out=None, slots=None):
+    """uint8 frames [B, T, Hs, Ws, 3] on the GPU -> the uint8 clip [B, T, R, R, 3] that the reference's FVD script feeds the
+    I3D: `((video + 0.5) * 255).byte()` of the float clip, channels last.  `out` [Bout, T, R, R, 3] and `slots` as above."""
+    return _ingest(frames, R, out, slots, u8=True)
 
 
 class RawVideoBatch:
     """a collated batch of raw clips: `groups` = [(uint8 [b, T, Hs, Ws, 3], batch slots [b])], one group per source size, in
-    order of first appearance; `to_video()` runs the ingest once per group into one [B, 3, T, R, R] tensor."""
+    order of first appearance; `to_video()` runs the ingest once per group into one [B, 3, T, R, R] tensor, `to_clip_u8()` into
+    one uint8 [B, T, R, R, 3] tensor."""
 
     def __init__(self, groups, batch_size, resolution):
         self.groups, self.batch_size, self.resolution = groups, int(batch_size), int(resolution)
@@ -199,14 +233,21 @@ class RawVideoBatch:
         return RawVideoBatch([(f.to(device, non_blocking=non_blocking), s.to(device, non_blocking=non_blocking))
                               for f, s in self.groups], self.batch_size, self.resolution)
 
-    def to_video(self):
+    def _ingest(self, u8):
         f0 = self.groups[0][0]
         if len(self.groups) == 1 and self.groups[0][1].numel() == self.batch_size:
-            return frames_to_video(f0, self.resolution)         # one size: the collate keeps batch order
-        out = torch.empty(self.shape, device=f0.device, dtype=torch.float32)
+            return _ingest(f0, self.resolution, None, None, u8)   # one size: the collate keeps batch order
+        B, C, T, R, _ = self.shape
+        out = torch.empty((B, T, R, R, C) if u8 else self.shape, device=f0.device, dtype=torch.uint8 if u8 else torch.float32)
         for f, s in self.groups:
-            frames_to_video(f, self.resolution, out=out, slots=s)
+            _ingest(f, self.resolution, out, s, u8)
         return out
+
+    def to_video(self):
+        return self._ingest(False)
+
+    def to_clip_u8(self):
+        return self._ingest(True)
 
 
 def collate_raw(items, resolution):

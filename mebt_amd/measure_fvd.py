@@ -7,8 +7,19 @@ if the file exists, else compute and write them), `--i3d_ckpt`, `--i3d_dtype {f1
 
 Fake side, as the reference: the batch size is forced to 32, batches are cycled until `n_sample` clips are embedded, `--score_file`
 keeps the top-`n_sample` videos by score, and when T != sequence_length * sample_fake_n_frames every batch takes a random start and
-every `sample_fake_n_frames`-th frame.  Real side: the pixel-video datasets of the reference are not part of this project;
-`--data_path` names a uint8 [N, T, H, W, C] .npy of real clips (the first `sequence_length` frames of the first `n_sample` clips).
+every `sample_fake_n_frames`-th frame.
+
+Real side, the first that applies:
+  1. `--real_embeddings FILE` exists: its logits.
+  2. `--image_folder` and `--data_path` is a frame folder (a directory with train.txt under `--train`, else test.txt): the reference's
+     route.  `VideoData(args, True)` is walked again and again (every pass a new shuffle and new start frames) in batches of 32; a
+     batch counts only if its size is a multiple of 16 (the reference's MAX_BATCH), every batch that counts counts as 32 towards
+     `n_sample`, and the result is cut to `n_sample`.  The workers only decode; crop, resize and the reference's
+     `((video + 0.5) * 255).byte()` run in the frame-ingest kernel (mebt_amd/frames.py:frames_to_clip_u8) and the clip goes to the
+     I3D without visiting the host.  Unlike the reference this warns when fewer than `n_sample` clips result and exits when a
+     whole pass yields no batch (the reference loops forever).
+  3. `--data_path` names a uint8 [N, T, H, W, C] .npy of real clips (the first `sequence_length` frames of the first `n_sample`
+     clips).
 Output: `<np_file>_consq_set_<n_neighbor>.csv` with pandas' to_csv layout (`,FVD,KVD` / `0,<fvd>,<kvd>`).
 """
 import argparse
@@ -21,6 +32,8 @@ import numpy as np
 import torch
 
 from .data import TokenData
+
+REF_MAX_BATCH = 16          # the reference's fvd.MAX_BATCH: its real loop skips a batch whose size is no multiple of it
 
 
 def build_parser(sliding=False):
@@ -74,6 +87,37 @@ def load_fake(args):
     return all_data_np
 
 
+def frame_folder(args):
+    """--image_folder with --data_path a directory that holds the list file of the chosen split"""
+    return bool(args.image_folder and os.path.isfile(os.path.join(args.data_path, 'train.txt' if args.train else 'test.txt')))
+
+
+def real_batches(args):
+    """the batches of the reference's real loop (measure_fvd_with_numpy.py:55-67) as `frames.RawVideoBatch`es on the host"""
+    from .config import AttrDict
+    from .data import VideoData
+    if args.sequence_length < 1:
+        raise SystemExit(f'--sequence_length {args.sequence_length}: whole-video clips differ in length and do not stack')
+    data = VideoData(AttrDict(vars(args)), True, raw=True)
+    loader = data.train_dataloader() if args.train else data.val_dataloader()
+    used = clips = 0
+    while True:
+        before = used
+        for batch in loader:
+            if len(batch['video']) % REF_MAX_BATCH == 0:
+                used += 1
+                clips += len(batch['video'])
+                yield batch['video']
+            if used * args.batch_size >= args.n_sample:         # every batch that counts counts as a full one
+                if clips < args.n_sample:
+                    print(f'warning: the real set holds {clips} clips, fewer than --n_sample {args.n_sample}')
+                return
+        if used == before:
+            raise SystemExit(f'--data_path {args.data_path}: a whole pass over the {"train" if args.train else "test"} list gave no batch '
+                             f'of a multiple of {REF_MAX_BATCH} clips (batches of {args.batch_size}); it needs at least '
+                             f'{REF_MAX_BATCH} videos')
+
+
 def real_embeddings(args, i3d, device):
     from .fvd import get_fvd_logits
     if args.real_embeddings and os.path.isfile(args.real_embeddings):
@@ -83,17 +127,24 @@ def real_embeddings(args, i3d, device):
             raise SystemExit(f'{args.real_embeddings} holds {len(emb)} embeddings, fewer than --n_sample {args.n_sample}')
         return torch.from_numpy(emb[:args.n_sample]).to(device)
     path = args.data_path
-    if not (path.endswith('.npy') and os.path.isfile(path)):
-        raise SystemExit(f"--data_path {path!r}: the real side reads a uint8 [N, T, H, W, C] .npy of real clips (the reference's "
-                         "HDF5 / frame-folder video datasets are not part of this project); or pass --real_embeddings FILE.npy")
-    real = np.load(path, mmap_mode='r')
-    if real.dtype != np.uint8 or real.ndim != 5:
-        raise SystemExit(f'--data_path {path}: expected uint8 [N, T, H, W, C], got {real.dtype} {real.shape}')
-    if real.shape[1] < args.sequence_length:
-        raise SystemExit(f'--data_path {path}: clips of {real.shape[1]} frames, shorter than --sequence_length {args.sequence_length}')
-    n = min(args.n_sample, len(real))
-    print('computing fvd embeddings for real videos')
-    emb = get_fvd_logits(real[:n, :args.sequence_length], i3d=i3d, device=device, batch=args.i3d_batch)
+    if frame_folder(args):
+        print('computing fvd embeddings for real videos')
+        emb = [get_fvd_logits(raw.to(device, non_blocking=True).to_clip_u8(), i3d=i3d, device=device, batch=args.i3d_batch)
+               for raw in real_batches(args)]
+        emb = torch.cat(emb, 0)[:args.n_sample]
+    elif path.endswith('.npy') and os.path.isfile(path):
+        real = np.load(path, mmap_mode='r')
+        if real.dtype != np.uint8 or real.ndim != 5:
+            raise SystemExit(f'--data_path {path}: expected uint8 [N, T, H, W, C], got {real.dtype} {real.shape}')
+        if real.shape[1] < args.sequence_length:
+            raise SystemExit(f'--data_path {path}: clips of {real.shape[1]} frames, shorter than --sequence_length {args.sequence_length}')
+        n = min(args.n_sample, len(real))
+        print('computing fvd embeddings for real videos')
+        emb = get_fvd_logits(real[:n, :args.sequence_length], i3d=i3d, device=device, batch=args.i3d_batch)
+    else:
+        raise SystemExit(f"--data_path {path!r}: the real side reads --real_embeddings FILE.npy if it exists, else a frame folder "
+                         "(--image_folder with a directory holding train.txt under --train, else test.txt), else a uint8 "
+                         "[N, T, H, W, C] .npy of real clips")
     if args.real_embeddings:
         np.save(args.real_embeddings, emb.cpu().numpy())
         print(f'wrote real embeddings {tuple(emb.shape)} to {args.real_embeddings}')

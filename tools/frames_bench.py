@@ -4,6 +4,8 @@
   ingest   the frame-ingest kernel (csrc/frames/frames.hip) on B x T uint8 frames -> [B, 3, T, R, R] fp32: median / min time per
            launch from HIP events around `--reps` back-to-back launches, and the effective GB/s (uint8 bytes read once +
            fp32 bytes written, over the kernel time), for 128x128 -> 128 and 240x320 -> 128 (UCF frames)
+  ingest_u8  the same launches with the uint8 output of the FVD real side, [B, T, R, R, 3] (a quarter of the bytes written), timed
+           right after the float output of the same shape
   step     ms per training step at the Sky-16f geometry (B 6, 16 x 128 x 128 pixels -> 4 x 16 x 16 tokens, bf16): the pixel
            path (raw uint8 240x320 frames -> ingest -> VQGAN.encode -> token step) against the token step on the ids of the
            same clips, one model, the two paths alternating step by step; medians of `--steps` pairs after `--warmup`
@@ -35,25 +37,26 @@ from mebt_amd import frames as F
 DEV = "cuda"
 
 
-def bench_ingest(B, T, H, W, R, reps):
+def bench_ingest(B, T, H, W, R, reps, u8=False):
     rs = np.random.RandomState(0)
     x = torch.from_numpy(rs.randint(0, 256, (B, T, H, W, 3)).astype(np.uint8)).to(DEV)
-    out = F.frames_to_video(x, R)
+    ingest = F.frames_to_clip_u8 if u8 else F.frames_to_video
+    out = ingest(x, R)
     for _ in range(5):
-        F.frames_to_video(x, R, out=out)
+        ingest(x, R, out=out)
     torch.cuda.synchronize()
     times = []
     for _ in range(5):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(reps):
-            F.frames_to_video(x, R, out=out)
+            ingest(x, R, out=out)
         e1.record()
         e1.synchronize()
         times.append(e0.elapsed_time(e1) / reps * 1e3)
-    nbytes = x.numel() + out.numel() * 4
+    nbytes = x.numel() + out.numel() * out.element_size()
     med = statistics.median(times)
-    return {"bench": "ingest", "frames": B * T, "src": [H, W], "R": R, "us_median": round(med, 2), "us_min": round(min(times), 2),
+    return {"bench": "ingest_u8" if u8 else "ingest", "frames": B * T, "src": [H, W], "R": R, "us_median": round(med, 2), "us_min": round(min(times), 2),
             "MB_moved": round(nbytes / 1e6, 2), "GBps": round(nbytes / (med * 1e-6) / 1e9, 1)}
 
 
@@ -169,8 +172,9 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench measures on the GPU: no device visible")
-    print(json.dumps(bench_ingest(6, 16, 128, 128, 128, args.reps)), flush=True)
-    print(json.dumps(bench_ingest(6, 16, 240, 320, 128, args.reps)), flush=True)
+    for shape in ((6, 16, 128, 128, 128), (6, 16, 240, 320, 128)):
+        for u8 in (False, True):
+            print(json.dumps(bench_ingest(*shape, args.reps, u8=u8)), flush=True)
     if not args.no_step:
         print(json.dumps(bench_step(args.steps, args.warmup)), flush=True)
     if not args.no_loader:
