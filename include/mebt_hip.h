@@ -345,6 +345,17 @@ int mebt_op_frames_to_video(const uint8_t* frames, float* out, int32_t N, int32_
 int mebt_op_frames_to_clip_u8(const uint8_t* frames, uint8_t* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
                               int32_t S, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span, const uint8_t* lut,
                               const int32_t* slots, int32_t Bout, mebt_stream_t stream);
+/* ---- packed frame datasets (mebt_amd/packed.py): clips gathered from a pack of prepared frames ------------------------------------
+ * pack: uint8 [F, R, R, 3] in device memory, every frame after the crop and resize above; ids: int64 [B, T] on the device, row
+ * numbers into the pack.  out [B, 3, T, R, R] fp32 = lut[pack[ids]] (`lut` [256] as for mebt_op_frames_to_video): given the same bytes,
+ * what mebt_op_frames_to_video writes.  An id outside [0, F) writes nothing for that frame and reads nothing; all offsets into the
+ * pack are 64-bit (a resident pack is tens of GB).  The pack pointer needs no alignment. */
+int mebt_op_pack_to_video(const uint8_t* pack, int64_t F, const int64_t* ids, float* out, int32_t B, int32_t T, int32_t R,
+                          const float* lut, mebt_stream_t stream);
+/* The same gather through the uint8 table `lut` [256] -> out [B, T, R, R, 3] uint8, the clip layout of mebt_op_i3d_preprocess: given the
+ * same bytes, what mebt_op_frames_to_clip_u8 writes. */
+int mebt_op_pack_to_clip_u8(const uint8_t* pack, int64_t F, const int64_t* ids, uint8_t* out, int32_t B, int32_t T, int32_t R,
+                            const uint8_t* lut, mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

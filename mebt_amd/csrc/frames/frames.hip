@@ -188,6 +188,76 @@ __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* 
     }
 }
 
+// ---- packed frame datasets (mebt_amd/packed.py): gather rows of a pack [F, R, R, 3] uint8 by id --------------------------------------
+// The pack holds every frame after crop + resize, so a training clip is T rows of it and the only work left is the table lookup and the
+// layout: the same outputs as the copy kernel above, with the source frame chosen by ids[n] instead of n.  One workgroup per (frame,
+// chunk of PK_CHUNK bytes of it): the chunk is staged in LDS with 16-byte loads over its 16-byte-aligned body (single bytes for the at
+// most 15 bytes before and after it; the LDS copy keeps the global address' offset mod 16, so any pack pointer and any R work), then
+// read back a pixel (float: three planes, lanes along W) or a dword of the output run (uint8) per lane.  Every offset into the pack
+// is 64-bit; an id outside [0, F) writes nothing.
+constexpr int PK_CHUNK = 6144;              // 2048 pixels, or 1536 dwords of the uint8 run; a multiple of 3, 4 and 16
+
+template <typename Out>
+__global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* __restrict__ pack, int64_t F, const int64_t* __restrict__ ids,
+                                                                 Out* __restrict__ out, int T, int R, int nchunk, const Out* __restrict__ lut) {
+    __shared__ __attribute__((aligned(16))) uint8_t buf[PK_CHUNK + 16];
+    __shared__ Out lut_s[256];
+    const int64_t n = blockIdx.x / nchunk;
+    const int k = (int)(blockIdx.x - n * nchunk);
+    const int64_t id = ids[n];
+    if (id < 0 || id >= F) return;            // uniform over the block
+    const int tid = threadIdx.x;
+    const int nrun = R * R * 3;
+    const uint8_t* src = pack + (size_t)id * (size_t)nrun;
+    uint8_t* run = nullptr;
+    int mis = 0;
+    if constexpr (sizeof(Out) == 1) {
+        run = reinterpret_cast<uint8_t*>(out) + (size_t)n * (size_t)nrun;
+        mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
+    }
+    // this block's bytes of the frame: [c0, c1); the uint8 chunks are counted in dwords of the output run, which starts `mis` early
+    const int c0 = max(k * PK_CHUNK - mis, 0), c1 = min((k + 1) * PK_CHUNK - mis, nrun);
+    if (c0 >= c1) return;
+    lut_s[tid] = lut[tid];
+    const uint8_t* a = src + c0;
+    const int len = c1 - c0;
+    const int sh = (int)(reinterpret_cast<uintptr_t>(a) & 15);           // buf[sh + j] = a[j]: a + j and buf + sh + j agree mod 16
+    const int head = min((16 - sh) & 15, len);
+    const int nvec = (len - head) >> 4;
+    const int tail = head + nvec * 16;
+    for (int i = tid; i < nvec; i += FR_THREADS)
+        *reinterpret_cast<uint4*>(buf + sh + head + 16 * i) = *reinterpret_cast<const uint4*>(a + head + 16 * i);
+    if (tid < head) buf[sh + tid] = a[tid];
+    if (tid < len - tail) buf[sh + tail + tid] = a[tail + tid];
+    __syncthreads();
+    const int s0 = sh - c0;                   // buf[s0 + j] = byte j of the frame, c0 <= j < c1
+
+    if constexpr (sizeof(Out) == 1) {
+        for (int j = k * PK_CHUNK - mis + 4 * tid; j < c1; j += 4 * FR_THREADS) {
+            uint32_t v = 0;
+            if (j >= c0 && j + 4 <= c1) {
+                const uint8_t* s = buf + s0 + j;
+                v = (uint32_t)lut_s[s[0]] | (uint32_t)lut_s[s[1]] << 8 | (uint32_t)lut_s[s[2]] << 16 | (uint32_t)lut_s[s[3]] << 24;
+            } else {                           // a ragged end of the run
+                for (int c = 0; c < 4; ++c)
+                    if (j + c >= c0 && j + c < c1) v |= (uint32_t)lut_s[buf[s0 + j + c]] << (8 * c);
+            }
+            store_quad(run, j, nrun, v);
+        }
+        return;
+    }
+    const size_t plane = (size_t)R * R;
+    const int64_t b = n / T;
+    const int t = (int)(n - b * T);
+    Out* o = out + ((size_t)b * 3 * T + t) * plane;                      // channel c at o + c * T * plane
+    for (int p = c0 / 3 + tid; p < c1 / 3; p += FR_THREADS) {
+        const uint8_t* s = buf + s0 + 3 * p;
+        o[p] = lut_s[s[0]];
+        o[(size_t)T * plane + p] = lut_s[s[1]];
+        o[2 * (size_t)T * plane + p] = lut_s[s[2]];
+    }
+}
+
 hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 int fail(const char* who, const char* what) {
@@ -223,6 +293,24 @@ int frames_launch(const char* who, const uint8_t* frames, Out* out, int32_t N, i
     return MEBT_OK;
 }
 
+template <typename Out>
+int pack_launch(const char* who, const uint8_t* pack, int64_t F, const int64_t* ids, Out* out, int32_t B, int32_t T, int32_t R, const Out* lut,
+                mebt_stream_t stream) {
+    if (!pack || !ids || !out || !lut) return fail(who, "null pointer");
+    if (F < 1 || B < 1 || T < 1 || R < 1) return fail(who, "bad shape");
+    if ((long)R * R * 3 > (1l << 30)) return fail(who, "frame too large");       // a frame's bytes are indexed in int
+    // a uint8 run starts up to `slack` bytes after the dword boundary its chunks are counted from: every run shares out's offset when
+    // a frame is a whole number of dwords, else any offset occurs
+    const long nrun = (long)R * R * 3;
+    const long slack = sizeof(Out) == 1 ? (nrun % 4 ? 3 : (long)(reinterpret_cast<uintptr_t>(out) & 3)) : 0;
+    const long nchunk = (nrun + slack + PK_CHUNK - 1) / PK_CHUNK;
+    const long blocks = (long)B * T * nchunk;
+    if (blocks > (1l << 24)) return fail(who, "too many frames for one launch");      // grid.x * 256 threads stays below 2^32
+    hipLaunchKernelGGL(pack_gather_kernel<Out>, dim3((unsigned)blocks), dim3(FR_THREADS), 0, S(stream), pack, F, ids, out, T, R, (int)nchunk, lut);
+    MEBT_HIP_CHECK(hipGetLastError());
+    return MEBT_OK;
+}
+
 }  // namespace
 
 extern "C" int mebt_op_frames_to_video(const uint8_t* frames, float* out, int32_t N, int32_t T, int32_t Hs, int32_t Ws, int32_t y0, int32_t x0,
@@ -235,4 +323,14 @@ extern "C" int mebt_op_frames_to_clip_u8(const uint8_t* frames, uint8_t* out, in
                                          int32_t x0, int32_t S_, int32_t R, const int32_t* tab, int32_t K, int32_t rows, int32_t span,
                                          const uint8_t* lut, const int32_t* slots, int32_t Bout, mebt_stream_t stream) {
     return frames_launch<uint8_t>("frames_to_clip_u8", frames, out, N, T, Hs, Ws, y0, x0, S_, R, tab, K, rows, span, lut, slots, Bout, stream);
+}
+
+extern "C" int mebt_op_pack_to_video(const uint8_t* pack, int64_t F, const int64_t* ids, float* out, int32_t B, int32_t T, int32_t R,
+                                     const float* lut, mebt_stream_t stream) {
+    return pack_launch<float>("pack_to_video", pack, F, ids, out, B, T, R, lut, stream);
+}
+
+extern "C" int mebt_op_pack_to_clip_u8(const uint8_t* pack, int64_t F, const int64_t* ids, uint8_t* out, int32_t B, int32_t T, int32_t R,
+                                       const uint8_t* lut, mebt_stream_t stream) {
+    return pack_launch<uint8_t>("pack_to_clip_u8", pack, F, ids, out, B, T, R, lut, stream);
 }

@@ -293,16 +293,23 @@ def _arg(a, k, d):
 class VideoData(TokenData):
     """reference VideoData._dataset (data.py:248-273): `vtokens` -> token clips (TokenClipDataset, in latent units as the
     launcher passes them), `image_folder` -> FrameListDataset (in pixel units).  raw=True makes the frame loader return
-    uint8 source-size clips collated by `frames.collate_raw` for the GPU ingest."""
+    uint8 source-size clips collated by `frames.collate_raw` for the GPU ingest.  `packed_path` (with `image_folder`) reads the
+    folder's pack instead of its images (mebt_amd/packed.py): PackedFrameDataset, batches of pack rows."""
 
     def __init__(self, args, shuffle=True, world_size=1, rank=0, raw=False):
         super().__init__(args, shuffle=shuffle, world_size=world_size, rank=rank)
         self.raw = raw
+        self._packs = {}                    # train / test -> the opened (and, resident, uploaded) pack: one upload per split
 
     def _dataset(self, train):
         a = self.args
         if _arg(a, "vtokens", False):
             return super()._dataset(train)
+        if _arg(a, "image_folder", False) and _arg(a, "packed_path", None):
+            from .packed import PackedFrameDataset
+            return PackedFrameDataset(_arg(a, "data_path", None), _arg(a, "packed_path", None), _arg(a, "sequence_length", 16),
+                                      resolution=_arg(a, "resolution", 128), sample_every_n_frames=_arg(a, "sample_every_n_frames", 1),
+                                      train=train, latent_shape=_arg(a, "latent_shape", [1]))
         if _arg(a, "image_folder", False):
             return FrameListDataset(_arg(a, "data_path", None), _arg(a, "sequence_length", 16), resolution=_arg(a, "resolution", 128),
                                     sample_every_n_frames=_arg(a, "sample_every_n_frames", 1), train=train,
@@ -315,11 +322,29 @@ class VideoData(TokenData):
 
     def _dataloader(self, train):
         ds = self._dataset(train)
+        if _arg(self.args, "packed_path", None) and not hasattr(ds, "pack"):
+            raise ValueError("packed_path is the pack of a frame folder: it needs image_folder (--image_folder) and no vtokens")
         if not isinstance(ds, FrameListDataset):
             return super()._dataloader(train)
         a = self.args
         sampler = ShardedSampler(len(ds), self.world_size, self.rank) if self.world_size > 1 else None
         nw = _arg(a, "num_workers", 0)
+        if hasattr(ds, "pack"):
+            # a packed split (mebt_amd/packed.py): nothing to decode, so the loader runs in this process; resident mode uploads the
+            # split to this rank's device once and the batches carry row numbers only
+            from .packed import choose_resident, collate_packed
+            if train in self._packs:
+                ds.pack, resident = self._packs[train]
+            else:
+                resident, why = choose_resident(ds.pack, _arg(a, "packed_resident", "auto"))
+                print(why)
+                print(f"packed frames: the loader runs in-process, data.num_workers={nw} is ignored")
+                if resident:
+                    ds.pack.upload(torch.device("cuda", torch.cuda.current_device()))
+                self._packs[train] = (ds.pack, resident)
+            return torch.utils.data.DataLoader(ds, batch_size=_arg(a, "batch_size", 6), num_workers=0, pin_memory=True, sampler=sampler,
+                                               shuffle=sampler is None and self.shuffle,
+                                               collate_fn=functools.partial(collate_packed, pack=ds.pack, resident=resident))
         collate = None
         if self.raw:
             from .frames import collate_raw

@@ -166,8 +166,9 @@ def plan(Hs, Ws, R, device):
     return p
 
 
-def _ingest(frames, R, out, slots, u8):
-    """argument checks and launch of both outputs: float32 [B, 3, T, R, R], or (u8) uint8 [B, T, R, R, 3]"""
+def _ingest(frames, R, out, slots, u8, lut=None):
+    """argument checks and launch of both outputs: float32 [B, 3, T, R, R], or (u8) uint8 [B, T, R, R, 3]; `lut` replaces the
+    plan's 256-entry table of the output's dtype"""
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
         raise ValueError(f"frame ingest: expected uint8 [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_cuda:
@@ -189,12 +190,16 @@ def _ingest(frames, R, out, slots, u8):
     if slots is not None:
         if slots.dtype != torch.int32 or slots.numel() != B or slots.device != frames.device:
             raise ValueError("frame ingest: `slots` must be int32 [B] on the frames' device")
+    if lut is None:
+        lut = p.byte_lut if u8 else p.lut
+    elif lut.dtype != dtype or lut.numel() != 256 or lut.device != frames.device or not lut.is_contiguous():
+        raise ValueError(f"frame ingest: `lut` must be contiguous {str(dtype).split('.')[-1]} [256] on the frames' device")
     if B == 0:
         return out
     lib = _lib.load()
     _lib.check((lib.mebt_op_frames_to_clip_u8 if u8 else lib.mebt_op_frames_to_video)(
         _lib.ptr(frames), _lib.ptr(out), B * T, T, Hs, Ws, p.y0, p.x0, p.S, R, _lib.ptr(p.tab), p.K, p.rows, p.span,
-        _lib.ptr(p.byte_lut if u8 else p.lut), _lib.ptr(slots), int(out.shape[0]), _lib.cur_stream()))
+        _lib.ptr(lut), _lib.ptr(slots), int(out.shape[0]), _lib.cur_stream()))
     return out
 
 
@@ -204,10 +209,11 @@ def frames_to_video(frames, R, out=None, slots=None):
     return _ingest(frames, R, out, slots, u8=False)
 
 
-def frames_to_clip_u8(frames, R, out=None, slots=None):
+def frames_to_clip_u8(frames, R, out=None, slots=None, lut=None):
     """uint8 frames [B, T, Hs, Ws, 3] on the GPU -> the uint8 clip [B, T, R, R, 3] that the reference's FVD script feeds the
-    I3D: `((video + 0.5) * 255).byte()` of the float clip, channels last.  `out` [Bout, T, R, R, 3] and `slots` as above."""
-    return _ingest(frames, R, out, slots, u8=True)
+    I3D: `((video + 0.5) * 255).byte()` of the float clip, channels last.  `out` [Bout, T, R, R, 3] and `slots` as above.
+    `lut` (uint8 [256] on the device) replaces `byte_table`: the identity gives PIL's own bytes (mebt_amd/packed.py)."""
+    return _ingest(frames, R, out, slots, u8=True, lut=lut)
 
 
 class RawVideoBatch:

@@ -17,7 +17,8 @@ Real side, the first that applies:
      `n_sample`, and the result is cut to `n_sample`.  The workers only decode; crop, resize and the reference's
      `((video + 0.5) * 255).byte()` run in the frame-ingest kernel (mebt_amd/frames.py:frames_to_clip_u8) and the clip goes to the
      I3D without visiting the host.  Unlike the reference this warns when fewer than `n_sample` clips result and exits when a
-     whole pass yields no batch (the reference loops forever).
+     whole pass yields no batch (the reference loops forever).  With `--packed_path DIR` the same batches are drawn by the same
+     rule from the folder's pack (mebt_amd/packed.py) and gathered on the GPU: the same bytes in the same order, nothing decoded.
   3. `--data_path` names a uint8 [N, T, H, W, C] .npy of real clips (the first `sequence_length` frames of the first `n_sample`
      clips).
 Output: `<np_file>_consq_set_<n_neighbor>.csv` with pandas' to_csv layout (`,FVD,KVD` / `0,<fvd>,<kvd>`).
@@ -54,6 +55,9 @@ def build_parser(sliding=False):
     parser.add_argument('--sample_fake_n_frames', type=int, default=1)
     parser.add_argument('--real_embeddings', type=str, default='',
                         help='.npy of the real set\'s [N, 400] I3D logits: loaded if it exists, else computed and written')
+    parser.add_argument('--packed_path', type=str, default='',
+                        help='with --image_folder: the pack of --data_path (python -m mebt_amd.pack_frames); the real clips are gathered '
+                             'from it instead of decoded')
     parser.add_argument('--i3d_ckpt', type=str, default=None,
                         help='I3D state_dict (default: $MEBT_I3D_CKPT, then mebt/fvd/i3d_pretrained_400.pt)')
     parser.add_argument('--i3d_dtype', type=str, default='f16', choices=['f16', 'f32'])
@@ -93,7 +97,8 @@ def frame_folder(args):
 
 
 def real_batches(args):
-    """the batches of the reference's real loop (measure_fvd_with_numpy.py:55-67) as `frames.RawVideoBatch`es on the host"""
+    """the batches of the reference's real loop (measure_fvd_with_numpy.py:55-67) as `frames.RawVideoBatch`es on the host (with
+    --packed_path: `packed.PackedVideoBatch`es, the same surface)"""
     from .config import AttrDict
     from .data import VideoData
     if args.sequence_length < 1:

@@ -1,7 +1,7 @@
 """`python -m mebt_amd.measure_sliding_fvd` — FVD / KVD of every `sequence_length`-frame window of long (128-frame) samples, one
 window start t every `--slide` frames over range(0, 128 - sequence_length) (reference measure_sliding_fvd_with_numpy.py), on the
-HIP I3D.  Flags and the real side as `mebt_amd.measure_fvd`: saved embeddings, a frame folder (`--image_folder`) or an .npy of
-clips.
+HIP I3D.  Flags and the real side as `mebt_amd.measure_fvd`: saved embeddings, a frame folder (`--image_folder`, or its pack
+with `--packed_path`) or an .npy of clips.
 
 Output: `<np_file>_slide<slide>_clip<sequence_length>_<n_neighbor>.csv` in pandas' to_csv layout with the columns t, fvd, kvd.
 The reference builds its DataFrame from these plus four empty columns (p, r, d, c) of another length, which pandas rejects;

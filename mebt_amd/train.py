@@ -11,7 +11,8 @@ exp.{exact_lr,warmup_steps,weight_decay,cosine_lr}, :45-66), seed 42 on every ra
 draw the same `t`; one process per GPU with RCCL all-reduce (DDP, :39-41).  Data: token grids from a
 `.npz` / `.h5` token file with the reference's `{train,test}_data` / `_idx` keys (`--tokens` or `data.data_path`,
 mebt_amd/data.py), frame folders (the shipped YAMLs' `image_folder: True`: `[VIDEO_ID]_[FRAME_NUM].png` files listed in
-`data.data_path`/train.txt and test.txt, tokenized each step by the frozen 3D-VQGAN of `model.vqvae.params.ckpt_path`)
+`data.data_path`/train.txt and test.txt, tokenized each step by the frozen 3D-VQGAN of `model.vqvae.params.ckpt_path`;
+`data.packed_path=DIR` reads the folder's pack from `python -m mebt_amd.pack_frames` instead of decoding the images)
 or synthetic grids; every item carries `indices = randperm(T*H*W)` like the reference datasets
 (mebt/data.py:85,233,413,471); ranks read disjoint shards (DistributedSampler semantics).
 Checkpoints use the Lightning layout {'state_dict','hyper_parameters','global_step','epoch'} plus 'mebt_amd_loop'
@@ -69,6 +70,12 @@ def frame_folder_data(dcfg, tokens=None):
         return False
     path = dcfg.get("data_path", None)
     return bool(path) and os.path.isdir(path) and os.path.isfile(os.path.join(path, "train.txt"))
+
+
+def packed_frame_data(dcfg, tokens=None):
+    """True when a frame-folder run reads the folder's pack (`data.packed_path`, python -m mebt_amd.pack_frames) instead of its
+    images: the list files still come from data_path."""
+    return frame_folder_data(dcfg, tokens) and bool(dcfg.get("packed_path", None))
 
 
 def check_first_stage(cfg):
@@ -166,6 +173,10 @@ def main():
         dargs["latent_shape"] = shape
         dargs.setdefault("batch_size", 6)
         data = VideoData(dargs, world_size=world, rank=rank, raw=True)
+        if packed_frame_data(dargs, args.tokens) and rank == 0:
+            # the same clips as rows of the folder's pack, gathered on the GPU (packed.py); a pack that does not match the list
+            # files or data.resolution raises with the command that rebuilds it
+            print(f"frame folder {dargs['data_path']}: clips come from the pack at {dargs['packed_path']}", flush=True)
     else:
         if args.tokens:
             dargs["data_path"] = args.tokens

@@ -12,9 +12,19 @@
   loader   FrameListDataset(raw=True) + collate_raw through a DataLoader with `--workers` workers on PNG frames written to a
            temporary directory: decoded frames per second, next to the frames per second one step of each path consumes
 
+  gather   the packed-dataset gather (csrc/frames/frames.hip: pack_gather_kernel) of 96 frames at R 128 with contiguous ids, float and
+           uint8 output, against the copy kernel (the 128 -> 128 `ingest` case) on the same 96 frames laid out contiguously: the two
+           alternate round by round, each round event-timed over `--reps` launches; medians, the copy kernel's own run-to-run
+           spread, effective GB/s.  The 4.7 MB input stays in the Infinity Cache: these are not HBM figures.
+  pack_build / packed_loader   `packed.build_pack` (8 decode workers + the ingest kernel) on the loader leg's PNG folder, then the
+           packed loader in host and in resident mode on that pack: frames per second of the batches alone (comparable with
+           `loader`) and with the move to the device, the gather and a synchronise per batch
+  step     with the pack at hand also `packed`: next(loader) + move + step from the resident pack, in the same rotation as the pixel
+           and token steps; `packed_minus_pixel_ms` is the median of the paired differences, next to the pairs' spread
+
 The transformer and the VQGAN have random weights (time does not depend on them); the PNGs are smooth random images.
 
-Usage:  python tools/frames_bench.py [--steps 10] [--warmup 3] [--reps 50] [--workers 8] [--no-step] [--no-loader]
+Usage:  python tools/frames_bench.py [--steps 10] [--warmup 3] [--reps 50] [--workers 8 16] [--no-step] [--no-loader] [--no-packed]
 """
 import argparse
 import json
@@ -60,6 +70,76 @@ def bench_ingest(B, T, H, W, R, reps, u8=False):
             "MB_moved": round(nbytes / 1e6, 2), "GBps": round(nbytes / (med * 1e-6) / 1e9, 1)}
 
 
+def clocks():
+    """the device's current clocks as rocm-smi shows them (read only), for the record"""
+    import subprocess
+    try:
+        out = subprocess.run(["rocm-smi", "-d", "0", "--showclocks"], capture_output=True, text=True, timeout=60).stdout
+        return [" ".join(ln.split()) for ln in out.splitlines() if "sclk" in ln or "mclk" in ln or "fclk" in ln]
+    except Exception as e:                                           # noqa: BLE001
+        return [f"not read: {e}"]
+
+
+def bench_gather(reps, rounds=9, B=6, T=16, R=128):
+    """B x T frames; B 6 is the training batch, where a launch is shorter than the host takes to issue the next (see
+    `host_us_per_launch`: event time per launch then equals the launch rate), B 96 makes both kernels run longer than that"""
+    from mebt_amd import packed as P
+    rs = np.random.RandomState(0)
+    x = torch.from_numpy(rs.randint(0, 256, (B, T, R, R, 3)).astype(np.uint8)).to(DEV)
+    pack = x.view(B * T, R, R, 3)
+    ids = torch.arange(B * T, device=DEV).view(B, T)
+    out = []
+    for u8 in (False, True):
+        copy_out = (F.frames_to_clip_u8 if u8 else F.frames_to_video)(x, R)
+        assert torch.equal(copy_out, (P.pack_to_clip_u8 if u8 else P.pack_to_video)(pack, ids, R))
+
+        def copy():
+            (F.frames_to_clip_u8 if u8 else F.frames_to_video)(x, R, out=copy_out)
+
+        gather_out = torch.empty_like(copy_out)
+
+        def gather():
+            (P.pack_to_clip_u8 if u8 else P.pack_to_video)(pack, ids, R, out=gather_out)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / reps * 1e3
+
+        def host(fn):                                                # host time to issue one launch, queue never full
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(20):
+                fn()
+            dt = (time.perf_counter() - t0) / 20 * 1e6
+            torch.cuda.synchronize()
+            return dt
+
+        for _ in range(3):
+            timed(copy), timed(gather)
+        tc, tg = [], []
+        for r in range(rounds):                                      # alternate which kernel goes first
+            if r % 2 == 0:
+                tc.append(timed(copy)); tg.append(timed(gather))
+            else:
+                tg.append(timed(gather)); tc.append(timed(copy))
+        nbytes = x.numel() + copy_out.numel() * copy_out.element_size()
+        mc, mg = statistics.median(tc), statistics.median(tg)
+        out.append({"bench": "gather_u8" if u8 else "gather", "frames": B * T, "R": R, "reps": reps, "rounds": rounds,
+                    "copy_us_median": round(mc, 2), "gather_us_median": round(mg, 2),
+                    "copy_us_min_max": [round(min(tc), 2), round(max(tc), 2)], "gather_us_min_max": [round(min(tg), 2), round(max(tg), 2)],
+                    "gather_minus_copy_us_paired_median": round(statistics.median([g - c for g, c in zip(tg, tc)]), 2),
+                    "copy_spread_us": round(max(tc) - min(tc), 2), "MB_moved": round(nbytes / 1e6, 2),
+                    "host_us_per_launch": {"copy": round(host(copy), 2), "gather": round(host(gather), 2)},
+                    "copy_GBps": round(nbytes / (mc * 1e-6) / 1e9, 1), "gather_GBps": round(nbytes / (mg * 1e-6) / 1e9, 1),
+                    "note": "back-to-back launches into a preallocated output, each wrapper's host path included; the input stays in the Infinity Cache"})
+    return out
+
+
 def smooth_frames(rs, n, H, W):
     """random low-frequency RGB frames (PNG-compressible like natural images, unlike uniform noise)"""
     small = rs.randint(0, 256, (n, H // 8 + 1, W // 8 + 1, 3)).astype(np.float32)
@@ -67,7 +147,7 @@ def smooth_frames(rs, n, H, W):
     return np.clip(big + rs.randint(-6, 7, big.shape), 0, 255).astype(np.uint8)
 
 
-def bench_step(steps, warmup):
+def bench_step(steps, warmup, packed_loader=None):
     from mebt_amd import presets
     from mebt_amd.trainer import TrainLoop
     from mebt_amd.vqgan import VQGAN
@@ -86,22 +166,39 @@ def bench_step(steps, warmup):
     ids = vq.encode(batch.to(DEV).to_video())
     random.seed(0)
 
+    pk_it = [iter(packed_loader)] if packed_loader is not None else None
+
     def run(kind):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        x = batch.to(DEV, non_blocking=True) if kind == "pixel" else ids
-        loop.step(x, idx)
+        if kind == "packed":                # the loop a run from a resident pack executes: draw + collate, ids to the device, step
+            try:
+                pb = next(pk_it[0])
+            except StopIteration:
+                pk_it[0] = iter(packed_loader)
+                pb = next(pk_it[0])
+            loop.step(pb["video"].to(DEV, non_blocking=True), pb["indices"].to(DEV, non_blocking=True))
+        else:
+            x = batch.to(DEV, non_blocking=True) if kind == "pixel" else ids
+            loop.step(x, idx)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3
 
+    kinds = ["pixel", "token"] + (["packed"] if packed_loader is not None else [])
     for _ in range(warmup):
-        run("pixel"), run("token")
-    px, tk = [], []
-    for i in range(steps):                  # alternate which path goes first in each pair
-        if i % 2 == 0:
-            px.append(run("pixel")); tk.append(run("token"))
-        else:
-            tk.append(run("token")); px.append(run("pixel"))
+        for k in kinds:
+            run(k)
+    times = {k: [] for k in kinds}
+    for i in range(steps):                  # rotate which path goes first in each round
+        for k in kinds[i % len(kinds):] + kinds[:i % len(kinds)]:
+            times[k].append(run(k))
+    px, tk = times["pixel"], times["token"]
+    packed = {}
+    if packed_loader is not None:
+        diff = sorted(a - b for a, b in zip(times["packed"], px))
+        packed = {"packed_ms_median": round(statistics.median(times["packed"]), 3), "packed_ms": [round(v, 3) for v in times["packed"]],
+                  "packed_minus_pixel_ms": round(statistics.median(diff), 3), "packed_minus_pixel_ms_min_max": [round(diff[0], 3), round(diff[-1], 3)],
+                  "pixel_ms_min_max": [round(min(px), 3), round(max(px), 3)]}
     # the pieces the pixel path adds, timed alone with events
     xd = batch.to(DEV)
     video = xd.to_video()
@@ -120,45 +217,92 @@ def bench_step(steps, warmup):
             "pixel_minus_token_ms": round(statistics.median([a - b for a, b in zip(px, tk)]), 3),
             "pixel_ms": [round(v, 3) for v in px], "token_ms": [round(v, 3) for v in tk],
             "vqgan_encode_ms_median": round(statistics.median(enc), 3), "h2d_uint8_ms_median": round(statistics.median(h2d), 3),
-            "h2d_MB": round(raw.numel() / 1e6, 2)}
+            "h2d_MB": round(raw.numel() / 1e6, 2), "pixel_frames_per_s": round(B * T / (statistics.median(px) * 1e-3), 1), **packed}
 
 
-def bench_loader(workers, videos=24, frames=40, batches=12):
+def write_folder(root, videos=24, frames=40):
+    """the loader legs' synthetic frame folder: `videos` videos of `frames` 240x320 PNGs, listed in train.txt"""
     from PIL import Image
-    from mebt_amd.data import VideoData
+    rs = np.random.RandomState(2)
+    paths = []
+    for v in range(videos):
+        for k, f in enumerate(smooth_frames(rs, frames, 240, 320)):
+            p = os.path.join(root, f"v{v:03d}_{k + 1:04d}.png")        # zero-padded: the list is sorted as strings
+            Image.fromarray(f).save(p, compress_level=1)
+            paths.append(p)
+    paths.append(os.path.join(root, "zz_1.png"))                     # the last video of a list is never flushed
+    Image.fromarray(f).save(paths[-1])
+    with open(os.path.join(root, "train.txt"), "w") as fh:
+        fh.write("\n".join(paths) + "\n")
+    return paths
+
+
+def loader_args(root, workers, **more):
     from mebt_amd.config import AttrDict
-    root = tempfile.mkdtemp(prefix="frames_bench_")
-    try:
-        rs = np.random.RandomState(2)
-        paths = []
-        for v in range(videos):
-            for k, f in enumerate(smooth_frames(rs, frames, 240, 320)):
-                p = os.path.join(root, f"v{v:03d}_{k + 1:04d}.png")    # zero-padded: the list is sorted as strings
-                Image.fromarray(f).save(p, compress_level=1)
-                paths.append(p)
-        paths.append(os.path.join(root, "zz_1.png"))                 # the last video of a list is never flushed
-        Image.fromarray(f).save(paths[-1])
-        with open(os.path.join(root, "train.txt"), "w") as fh:
-            fh.write("\n".join(paths) + "\n")
-        a = AttrDict(data_path=root, image_folder=True, sequence_length=16, resolution=128, latent_shape=[4, 16, 16], batch_size=6,
-                     num_workers=workers)
-        loader = VideoData(a, raw=True).train_dataloader()
-        n, t0, it = 0, None, iter(loader)
-        for b in range(batches + 2):
+    return AttrDict(data_path=root, image_folder=True, sequence_length=16, resolution=128, latent_shape=[4, 16, 16], batch_size=6,
+                    num_workers=workers, **more)
+
+
+def bench_loader(root, workers, batches=12):
+    from mebt_amd.data import VideoData
+    loader = VideoData(loader_args(root, workers), raw=True).train_dataloader()
+    n, t0, it = 0, None, iter(loader)
+    for b in range(batches + 2):
+        try:
+            batch = next(it)
+        except StopIteration:
+            it = iter(loader)
+            batch = next(it)
+        if b == 1:                                                   # after the workers' start-up
+            t0 = time.perf_counter()
+        elif b > 1:
+            n += sum(int(f.shape[0] * f.shape[1]) for f, _ in batch["video"].groups)
+    dt = time.perf_counter() - t0
+    first = os.path.join(root, "v000_0001.png")
+    return {"bench": "loader", "workers": workers, "src": [240, 320], "png_bytes_per_frame": os.path.getsize(first),
+            "frames_per_s": round(n / dt, 1), "batches_per_s": round(batches / dt, 2), "frames_per_batch": 96}
+
+
+def bench_pack_build(root, pack_dir, workers=8):
+    from mebt_amd import packed as P
+    t0 = time.perf_counter()
+    n = P.build_pack(root, pack_dir, 128, splits=["train"], resize=P.gpu_resize, num_workers=workers)["train"]
+    dt = time.perf_counter() - t0
+    return {"bench": "pack_build", "workers": workers, "frames": n, "src": [240, 320], "R": 128, "seconds": round(dt, 2),
+            "frames_per_s": round(n / dt, 1), "pack_bytes": os.path.getsize(os.path.join(pack_dir, "train_frames.npy"))}
+
+
+def packed_loader(root, pack_dir, resident):
+    from mebt_amd.data import VideoData
+    return VideoData(loader_args(root, 0, packed_path=pack_dir, packed_resident=resident), raw=True).train_dataloader()
+
+
+def bench_packed_loader(root, pack_dir, resident, batches=200):
+    loader = packed_loader(root, pack_dir, resident)
+
+    def walk(device):
+        n, it = 0, iter(loader)
+        next(it)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(batches):
             try:
                 batch = next(it)
             except StopIteration:
                 it = iter(loader)
                 batch = next(it)
-            if b == 1:                                               # after the workers' start-up
-                t0 = time.perf_counter()
-            elif b > 1:
-                n += sum(int(f.shape[0] * f.shape[1]) for f, _ in batch["video"].groups)
-        dt = time.perf_counter() - t0
-        return {"bench": "loader", "workers": workers, "src": [240, 320], "png_bytes_per_frame": os.path.getsize(paths[0]),
-                "frames_per_s": round(n / dt, 1), "batches_per_s": round(batches / dt, 2), "frames_per_batch": 96}
-    finally:
-        shutil.rmtree(root)
+            if device:
+                batch["video"].to(DEV, non_blocking=True).to_video()
+                torch.cuda.synchronize()
+            n += batch["video"].shape[0] * batch["video"].shape[2]
+        return n / (time.perf_counter() - t0)
+
+    walk(True)
+    host = [walk(False) for _ in range(3)]
+    dev = [walk(True) for _ in range(3)]
+    return {"bench": "packed_loader", "mode": "resident" if resident else "host", "batches": batches, "frames_per_batch": 96,
+            "frames_per_s": round(statistics.median(host), 1), "clips_per_s": round(statistics.median(host) / 16, 1),
+            "frames_per_s_to_device": round(statistics.median(dev), 1), "frames_per_s_to_device_min_max": [round(min(dev), 1), round(max(dev), 1)]}
 
 
 def main():
@@ -166,19 +310,39 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--workers", type=int, nargs="+", default=[8])
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-loader", action="store_true")
+    ap.add_argument("--no-packed", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench measures on the GPU: no device visible")
+    print(json.dumps({"bench": "clocks", "when": "start", "rocm_smi": clocks()}), flush=True)
     for shape in ((6, 16, 128, 128, 128), (6, 16, 240, 320, 128)):
         for u8 in (False, True):
             print(json.dumps(bench_ingest(*shape, args.reps, u8=u8)), flush=True)
-    if not args.no_step:
-        print(json.dumps(bench_step(args.steps, args.warmup)), flush=True)
-    if not args.no_loader:
-        print(json.dumps(bench_loader(args.workers)), flush=True)
+    if not args.no_packed:
+        for B in (6, 96):                                              # 96 frames (the step's batch), then 1536: kernel-bound
+            for row in bench_gather(args.reps if B == 6 else max(10, args.reps // 4), B=B):
+                print(json.dumps(row), flush=True)
+    root = tempfile.mkdtemp(prefix="frames_bench_")
+    try:
+        pack_dir = None
+        if not (args.no_loader and args.no_packed):
+            write_folder(root)
+        if not args.no_packed:
+            pack_dir = os.path.join(root, "pack")
+            print(json.dumps(bench_pack_build(root, pack_dir)), flush=True)
+            for resident in (False, True):
+                print(json.dumps(bench_packed_loader(root, pack_dir, resident)), flush=True)
+        if not args.no_step:
+            print(json.dumps(bench_step(args.steps, args.warmup, packed_loader(root, pack_dir, True) if pack_dir else None)), flush=True)
+        if not args.no_loader:
+            for w in args.workers:
+                print(json.dumps(bench_loader(root, w)), flush=True)
+    finally:
+        shutil.rmtree(root)
+    print(json.dumps({"bench": "clocks", "when": "end", "rocm_smi": clocks()}), flush=True)
 
 
 if __name__ == "__main__":
