@@ -356,6 +356,14 @@ int mebt_op_pack_to_video(const uint8_t* pack, int64_t F, const int64_t* ids, fl
  * same bytes, what mebt_op_frames_to_clip_u8 writes. */
 int mebt_op_pack_to_clip_u8(const uint8_t* pack, int64_t F, const int64_t* ids, uint8_t* out, int32_t B, int32_t T, int32_t R,
                             const uint8_t* lut, mebt_stream_t stream);
+/* ---- decoded video -> uint8 clip: what the sampling scripts keep of a first-stage decode -------------------------------------------
+ * in: fp32 [B, 3, Td, H, W], contiguous (VQGAN.decode); out: uint8 [B, T, H, W, 3], 1 <= T <= Td, the first T frames in the clip
+ * layout of mebt_op_i3d_preprocess.  u = (uint8) trunc((min(max(x, -0.5f), 0.5f) + 0.5f) * 255.0f), float32 throughout with the add and
+ * the multiply rounded separately: `torch.clamp(img, -0.5, 0.5) + 0.5` of the scripts, then numpy's float32 `* 255` and
+ * `.astype(np.uint8)`, bit for bit.  +-inf follow the clamp (0 and 255); NaN writes 0.  All offsets are 64-bit; `out` needs no
+ * alignment (rows of a larger store start at multiples of 3 T H W bytes). */
+int mebt_op_video_to_clip_u8(const float* in, uint8_t* out, int32_t B, int32_t Td, int32_t T, int32_t H, int32_t W,
+                             mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

@@ -88,6 +88,7 @@ PROTOTYPES = {
     "mebt_op_frames_to_clip_u8": (c_i32, [c_vp, c_vp] + [c_i32] * 8 + [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
     "mebt_op_pack_to_video": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mebt_op_pack_to_clip_u8": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mebt_op_video_to_clip_u8": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mebt_debug_dropout_mask": (c_i32, [C.c_uint64, C.c_uint32, c_f32, c_i64, c_vp, c_vp]),
     "mebt_debug_clock_probe": (c_i32, [c_vp, C.c_uint64, c_vp]),
     "mebt_debug_side_stream": (None, [c_vp, c_i32]),

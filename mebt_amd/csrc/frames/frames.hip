@@ -258,6 +258,55 @@ __global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* 
     }
 }
 
+// ---- decoded video -> uint8 clip (mebt_amd/frames.py:video_to_clip_u8): what the sampling scripts keep of a decode ---------------------
+// in fp32 [B, 3, Td, H, W] (VQGAN.decode) -> out uint8 [B, T, H, W, 3], the first T frames, u = (uint8) trunc((clamp(x, -0.5, 0.5) + 0.5)
+// * 255): the scripts' `torch.clamp(img, -0.5, 0.5) + 0.5`, then numpy's float32 `* 255` and `.astype(np.uint8)`.  Two separately rounded
+// float32 operations (__fadd_rn, __fmul_rn: never contracted into x * 255 + 127.5, which rounds differently); NaN writes 0.  One
+// workgroup per (frame, chunk of PK_CHUNK bytes of its run of H * W * 3 output bytes): the pixels the chunk touches are read from the
+// three planes, lanes along W, converted and interleaved in LDS, then read back a dword of the run per lane as in the gather above.
+__device__ __forceinline__ uint8_t video_byte(float x) {
+    const float c = fminf(fmaxf(x, -0.5f), 0.5f);           // fmaxf drops a NaN operand: NaN -> -0.5 -> 0
+    return (uint8_t)(int)__fmul_rn(__fadd_rn(c, 0.5f), 255.0f);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void video_to_clip_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int Td, int T,
+                                                                   int HW, int nchunk) {
+    __shared__ __attribute__((aligned(16))) uint8_t buf[PK_CHUNK + 16];
+    const int64_t n = blockIdx.x / nchunk;                   // output frame b * T + t
+    const int k = (int)(blockIdx.x - n * nchunk);
+    const int64_t b = n / T;
+    const int t = (int)(n - b * T);
+    const int tid = threadIdx.x;
+    const int nrun = HW * 3;
+    uint8_t* run = out + (size_t)n * (size_t)nrun;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
+    // this block's bytes of the frame: [c0, c1), counted in dwords of the output run, which starts `mis` early
+    const int c0 = max(k * PK_CHUNK - mis, 0), c1 = min((k + 1) * PK_CHUNK - mis, nrun);
+    if (c0 >= c1) return;                                    // uniform over the block
+    const int p0 = c0 / 3, p1 = (c1 + 2) / 3;                // the pixels those bytes belong to: at most PK_CHUNK / 3 + 2
+    const size_t plane = (size_t)Td * (size_t)HW;            // channel c of frame t at in + ((b * 3 + c) * Td + t) * HW
+    const float* src = in + ((size_t)b * 3 * Td + t) * (size_t)HW;
+    for (int p = p0 + tid; p < p1; p += FR_THREADS) {
+        uint8_t* d = buf + 3 * (p - p0);
+        d[0] = video_byte(src[p]);
+        d[1] = video_byte(src[plane + p]);
+        d[2] = video_byte(src[2 * plane + p]);
+    }
+    __syncthreads();
+    const int s0 = -3 * p0;                                  // buf[s0 + j] = byte j of the frame, c0 <= j < c1
+    for (int j = k * PK_CHUNK - mis + 4 * tid; j < c1; j += 4 * FR_THREADS) {
+        uint32_t v = 0;
+        if (j >= c0 && j + 4 <= c1) {
+            const uint8_t* s = buf + s0 + j;
+            v = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+        } else {                               // a ragged end of the run
+            for (int c = 0; c < 4; ++c)
+                if (j + c >= c0 && j + c < c1) v |= (uint32_t)buf[s0 + j + c] << (8 * c);
+        }
+        store_quad(run, j, nrun, v);
+    }
+}
+
 hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 int fail(const char* who, const char* what) {
@@ -333,4 +382,21 @@ extern "C" int mebt_op_pack_to_video(const uint8_t* pack, int64_t F, const int64
 extern "C" int mebt_op_pack_to_clip_u8(const uint8_t* pack, int64_t F, const int64_t* ids, uint8_t* out, int32_t B, int32_t T, int32_t R,
                                        const uint8_t* lut, mebt_stream_t stream) {
     return pack_launch<uint8_t>("pack_to_clip_u8", pack, F, ids, out, B, T, R, lut, stream);
+}
+
+extern "C" int mebt_op_video_to_clip_u8(const float* in, uint8_t* out, int32_t B, int32_t Td, int32_t T, int32_t H, int32_t W,
+                                        mebt_stream_t stream) {
+    const char* who = "video_to_clip_u8";
+    if (!in || !out) return fail(who, "null pointer");
+    if (B < 1 || Td < 1 || T < 1 || T > Td || H < 1 || W < 1) return fail(who, "bad shape");
+    if ((long)H * W * 3 > (1l << 30)) return fail(who, "frame too large");         // a frame's bytes are indexed in int
+    // a run starts up to `slack` bytes after the dword boundary its chunks are counted from, as in pack_launch
+    const long nrun = (long)H * W * 3;
+    const long slack = nrun % 4 ? 3 : (long)(reinterpret_cast<uintptr_t>(out) & 3);
+    const long nchunk = (nrun + slack + PK_CHUNK - 1) / PK_CHUNK;
+    const long blocks = (long)B * T * nchunk;
+    if (blocks > (1l << 24)) return fail(who, "too many frames for one launch");
+    hipLaunchKernelGGL(video_to_clip_kernel, dim3((unsigned)blocks), dim3(FR_THREADS), 0, S(stream), in, out, Td, T, H * W, (int)nchunk);
+    MEBT_HIP_CHECK(hipGetLastError());
+    return MEBT_OK;
 }

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs
+from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs, write_outputs_u8, ClipStore
 
 
 def build_parser():
@@ -33,12 +33,13 @@ def build_parser():
     return parser
 
 
-def apply_np_draft(args):
-    """reference :118-133: a given draft fixes n_draft (parsed from the file name) and disables the draft phase's sampling knobs"""
+def apply_np_draft(args, load=True):
+    """reference :118-133: a given draft fixes n_draft (parsed from the file name) and disables the draft phase's sampling knobs
+    (load=False: the names only, the file is not opened)"""
     postfix = ''
     if args.np_draft is None:
         return None, postfix
-    draft = np.load(args.np_draft)
+    draft = np.load(args.np_draft) if load else None
     if 'n_steps' in args.np_draft:
         args.n_draft = int(args.np_draft.split('VID_n_steps')[-1].split('_')[0])
     else:
@@ -65,17 +66,17 @@ def output_names(args, postfix):
     return f'{args.save}/videos_{args.total_length}/{args.dataset}/{tag}', f'{args.save}/numpy_files_{args.total_length}/{args.dataset}/{tag}'
 
 
-def main(argv=None):
-    from .config import load_config
+def n_clips(args, draft):
+    """clips one run decodes (what a ClipStore for it must hold)"""
+    n = (args.n_sample // args.batch_size + min(1, args.n_sample % args.batch_size)) * args.batch_size
+    return n if draft is None else min(n, len(draft))
+
+
+def run(args, gpt, resolution, draft, postfix, store=None, keep_np=True):
+    """the body of the script (:140-198) for a loaded model and the result of `apply_np_draft`.  With a `ClipStore` the pixel samples
+    go into it as uint8 clips made on the GPU and `write_outputs_u8` writes the same files.  Returns (save_np, the selected uint8
+    clips or None)."""
     from .sampling import draft_and_revise_sample
-    args, unknown = build_parser().parse_known_args(argv)
-    config = load_config(args.base, [u for u in unknown if "=" in u])
-    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
-    resolve_checkpoint(args)
-    print(args.gpt_ckpt)
-    draft, postfix = apply_np_draft(args)
-    os.makedirs(args.save, exist_ok=True)
-    gpt = load_model(args)
     save_dir, save_np = output_names(args, postfix)
     print('generating and saving video to %s...' % save_dir)
     os.makedirs(save_dir, exist_ok=True)
@@ -88,14 +89,18 @@ def main(argv=None):
             bs = args.batch_size if draft_batch is None else len(draft_batch)
             if bs == 0:
                 break
+            u8 = dict(samples_u8=store.target(bs)) if store is not None else {}
             logs = draft_and_revise_sample(gpt, bs, total_length=args.total_length, step_size=args.step_size, context_size=args.context_size,
                                            n_draft=args.n_draft, draft_t=args.draft_t, draft_k=args.draft_k, draft_p=args.draft_p,
                                            n_revise=args.n_revise, revise_t=args.revise_t, revise_k=args.revise_k, revise_p=args.revise_p,
-                                           M=args.M, draft=draft_batch)
+                                           M=args.M, draft=draft_batch, **u8)
             if "samples" in logs:
                 if args.save_videos and sample_id < args.save_n:
                     save_video_grid(logs['samples'], os.path.join(save_dir, 'generation_%d.%s' % (sample_id, args.format)), n_row)
-                all_data.append(logs['samples'].cpu().numpy())
+                if store is not None:
+                    store.put(logs['samples_u8'])
+                else:
+                    all_data.append(logs['samples'].cpu().numpy())
             all_code.append(logs['code_maps'].cpu().numpy())
             if args.verbose:
                 print(f"batch {sample_id + 1}/{n_batch}: code map {tuple(logs['code_maps'].shape)}", flush=True)
@@ -103,8 +108,26 @@ def main(argv=None):
         os.makedirs(os.path.dirname(save_np), exist_ok=True)
         with open(save_np + '.txt', 'w') as f:
             f.write(args.np_draft)
+    if store is not None:
+        return save_np, write_outputs_u8(args, save_np, store, all_code, keep_np=keep_np)
     write_outputs(args, save_np, all_data, all_code, resolution)
-    return save_np
+    return save_np, None
+
+
+def main(argv=None):
+    from .config import load_config
+    args, unknown = build_parser().parse_known_args(argv)
+    config = load_config(args.base, [u for u in unknown if "=" in u])
+    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+    resolve_checkpoint(args)
+    print(args.gpt_ckpt)
+    draft, postfix = apply_np_draft(args)
+    os.makedirs(args.save, exist_ok=True)
+    gpt = load_model(args)
+    store = None
+    if args.device_u8 and gpt.first_stage_model is not None and not args.no_np:
+        store = ClipStore(n_clips(args, draft), args.total_length, resolution, resolution, where=args.u8_store)
+    return run(args, gpt, resolution, draft, postfix, store)[0]
 
 
 if __name__ == "__main__":

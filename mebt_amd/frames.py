@@ -22,6 +22,11 @@ The real side of FVD / KVD wants the same clips as bytes: the reference turns th
 `((video + 0.5) * 255).byte()` (measure_fvd_with_numpy.py:63), which truncates and so moves some levels down by one.
 `frames_to_clip_u8` (`mebt_op_frames_to_clip_u8`) is the same kernel with that 256-entry byte table (`byte_table`) in place of the
 float one and the I3D path's clip layout [B, T, R, R, 3] as output; `clip_u8_twin` is its numpy statement.
+
+The fake side of FVD / KVD starts from a decode: the sampling scripts keep `torch.clamp(img, -0.5, 0.5) + 0.5` of the first stage's
+output as float32, and their writer makes bytes of it with numpy's float32 `* 255` and `.astype(np.uint8)`.  `video_to_clip_u8`
+(`mebt_op_video_to_clip_u8`) writes those bytes from the decoded tensor on the device, in the same clip layout, so a sample never
+visits the host as floats; `video_u8_twin` is its numpy statement.
 """
 import math
 
@@ -125,6 +130,15 @@ def clip_u8_twin(frames, R):
     return np.stack([lut[resize_twin(np.ascontiguousarray(f[y0:y0 + S, x0:x0 + S]), R)] for f in frames])
 
 
+def video_u8_twin(video, T):
+    """numpy twin of `video_to_clip_u8`: float32 [B, 3, Td, H, W] -> uint8 [B, T, H, W, 3] (tests only).  The scripts' own two
+    statements; fmax / fmin drop a NaN like the kernel does (NaN -> 0)."""
+    x = np.asarray(video.cpu() if torch.is_tensor(video) else video, dtype=np.float32)[:, :, :T]
+    with np.errstate(invalid="ignore"):
+        y = np.fmin(np.fmax(x, np.float32(-0.5)), np.float32(0.5)) + np.float32(0.5)
+        return np.ascontiguousarray(np.transpose((y * np.float32(255)).astype(np.uint8), (0, 2, 3, 4, 1)))
+
+
 # ---- device side ---------------------------------------------------------------------------------------------------------
 _plans = {}
 
@@ -214,6 +228,34 @@ def frames_to_clip_u8(frames, R, out=None, slots=None, lut=None):
     I3D: `((video + 0.5) * 255).byte()` of the float clip, channels last.  `out` [Bout, T, R, R, 3] and `slots` as above.
     `lut` (uint8 [256] on the device) replaces `byte_table`: the identity gives PIL's own bytes (mebt_amd/packed.py)."""
     return _ingest(frames, R, out, slots, u8=True, lut=lut)
+
+
+def video_to_clip_u8(video, T=None, out=None):
+    """a decoded video, float32 [B, 3, Td, H, W] on the GPU (VQGAN.decode) -> the uint8 clip [B, T, H, W, 3] of its first `T` frames
+    (default: all) that the sampling scripts save and the I3D reads: `(uint8)((clamp(x, -0.5, 0.5) + 0.5) * 255)` in float32, the
+    scripts' bytes.  `out`: a contiguous uint8 [B, T, H, W, 3] tensor or view on the same device (rows of a larger store)."""
+    if not torch.is_tensor(video) or video.dtype != torch.float32 or video.dim() != 5 or video.shape[1] != 3:
+        raise ValueError(f"video_to_clip_u8: expected float32 [B, 3, T, H, W], got {getattr(video, 'dtype', type(video))} "
+                         f"{tuple(getattr(video, 'shape', ()))}")
+    if not video.is_cuda:
+        raise ValueError("video_to_clip_u8 runs on the GPU: move the video to the device first")
+    if not video.is_contiguous():
+        raise ValueError("video_to_clip_u8: the video must be contiguous")
+    B, _, Td, H, W = video.shape
+    T = Td if T is None else int(T)
+    if not 1 <= T <= Td:
+        raise ValueError(f"video_to_clip_u8: T = {T} outside [1, {Td}]")
+    shape = (B, T, H, W, 3)
+    if out is None:
+        out = torch.empty(shape, device=video.device, dtype=torch.uint8)
+    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != video.device
+          or not out.is_contiguous()):
+        raise ValueError(f"video_to_clip_u8: `out` must be contiguous uint8 {list(shape)} on the video's device, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+    if B * H * W == 0:
+        return out
+    _lib.check(_lib.load().mebt_op_video_to_clip_u8(_lib.ptr(video), _lib.ptr(out), B, Td, T, H, W, _lib.cur_stream()))
+    return out
 
 
 class RawVideoBatch:

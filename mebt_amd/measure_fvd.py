@@ -157,7 +157,9 @@ def real_embeddings(args, i3d, device):
 
 
 def fake_embeddings(args, all_data_np, i3d, device, t0=None):
-    """the reference's fake loop: batches of args.batch_size (32), cycled until n_sample clips; t0 = the sliding window start"""
+    """the reference's fake loop: batches of args.batch_size (32), cycled until n_sample clips; t0 = the sliding window start.
+    `all_data_np`: uint8 [N, T, H, W, C], a numpy array or a torch tensor on the host or the device (mebt_amd/evaluate.py scores the
+    clips where the sampler left them)"""
     from .fvd import get_fvd_logits
     n_batch = all_data_np.shape[0] // args.batch_size
     if n_batch == 0:
@@ -174,7 +176,8 @@ def fake_embeddings(args, all_data_np, i3d, device, t0=None):
                 clip = all_data_np[sl, start_t:start_t + length:args.sample_fake_n_frames]
             else:
                 clip = all_data_np[sl]
-            out.append(get_fvd_logits(np.ascontiguousarray(clip), i3d=i3d, device=device, batch=args.i3d_batch))
+            clip = clip.contiguous() if torch.is_tensor(clip) else np.ascontiguousarray(clip)
+            out.append(get_fvd_logits(clip, i3d=i3d, device=device, batch=args.i3d_batch))
             n += args.batch_size
             if n >= args.n_sample:
                 break

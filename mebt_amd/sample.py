@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs
+from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs, write_outputs_u8, ClipStore
 
 
 def build_parser():
@@ -51,17 +51,18 @@ def output_names(args):
     return f'{args.save}/videos_{args.total_length}/{args.dataset}/{tag}', f'{args.save}/numpy_files_{args.total_length}/{args.dataset}/{tag}'
 
 
-def main(argv=None):
-    from .config import load_config
+def n_clips(args):
+    """clips one run decodes (what a ClipStore for it must hold)"""
+    if args.base_np:
+        return min(len(np.load(args.base_np, mmap_mode='r')), (args.n_sample // args.batch_size + 1) * args.batch_size)
+    return (args.n_sample // args.batch_size + 1) * args.batch_size
+
+
+def run(args, gpt, resolution, store=None, keep_np=True):
+    """the body of the script (:221-291) for a loaded model: sample, save the grids, write the outputs.  With a `ClipStore` the pixel
+    samples go into it as uint8 clips made on the GPU and `write_outputs_u8` writes the same files.  Returns (save_np, the selected
+    uint8 clips or None)."""
     from .sampling import bidirect_sample, extrapolate
-    args, unknown = build_parser().parse_known_args(argv)
-    config = load_config(args.base, [u for u in unknown if "=" in u])
-    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
-    resolve_checkpoint(args)
-    print(args.gpt_ckpt)
-    os.makedirs(args.save, exist_ok=True)
-    gpt = load_model(args)
-    gpt.mask_sampler.schedule = args.schedule                                   # :219
     save_dir, save_np = output_names(args)
     print('generating and saving video to %s...' % save_dir)
     os.makedirs(save_dir, exist_ok=True)
@@ -76,22 +77,45 @@ def main(argv=None):
     with torch.no_grad():
         for sample_id in range(n_batch):
             if vq_np is None:
-                logs = bidirect_sample(gpt, args.batch_size, **kw)
+                u8 = dict(samples_u8=store.target(args.batch_size)) if store is not None else {}
+                logs = bidirect_sample(gpt, args.batch_size, **kw, **u8)
             else:
                 vq_x = torch.as_tensor(vq_np[sample_id * args.batch_size:(sample_id + 1) * args.batch_size]).long().cuda()
                 if vq_x.shape[0] == 0:
                     break
-                logs = extrapolate(gpt, vq_x, **kw)
+                u8 = dict(samples_u8=store.target(vq_x.shape[0])) if store is not None else {}
+                logs = extrapolate(gpt, vq_x, **kw, **u8)
             if "samples" in logs:
                 if args.save_videos and sample_id < args.save_n:
                     save_video_grid(logs['samples'], os.path.join(save_dir, 'generation_%d.%s' % (sample_id, args.format)), n_row,
                                     fps=10 if vq_np is None else 30)
-                all_data.append(logs['samples'].cpu().numpy())
+                if store is not None:
+                    store.put(logs['samples_u8'])
+                else:
+                    all_data.append(logs['samples'].cpu().numpy())
             all_code.append(logs['code_maps'].cpu().numpy())
             if args.verbose:
                 print(f"batch {sample_id + 1}/{n_batch}: code map {tuple(logs['code_maps'].shape)}", flush=True)
+    if store is not None:
+        return save_np, write_outputs_u8(args, save_np, store, all_code, codemap_limit=args.n_sample, keep_np=keep_np)
     write_outputs(args, save_np, all_data, all_code, resolution, codemap_limit=args.n_sample)
-    return save_np
+    return save_np, None
+
+
+def main(argv=None):
+    from .config import load_config
+    args, unknown = build_parser().parse_known_args(argv)
+    config = load_config(args.base, [u for u in unknown if "=" in u])
+    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+    resolve_checkpoint(args)
+    print(args.gpt_ckpt)
+    os.makedirs(args.save, exist_ok=True)
+    gpt = load_model(args)
+    gpt.mask_sampler.schedule = args.schedule                                   # :219
+    store = None
+    if args.device_u8 and gpt.first_stage_model is not None and not args.no_np:
+        store = ClipStore(n_clips(args), args.total_length, resolution, resolution, where=args.u8_store)
+    return run(args, gpt, resolution, store)[0]
 
 
 if __name__ == "__main__":

@@ -11,21 +11,28 @@ import numpy as np
 import torch
 
 
-def _decode(model, code_map, total_length):
+def _decode(model, code_map, total_length, log, samples_u8=False):
+    """log['samples']: the first stage's decode as the reference keeps it; with `samples_u8` also log['samples_u8'], the uint8 clip
+    [B, total_length, H, W, 3] the scripts' writer would make of it, from the same decoded tensor (mebt_amd/frames.py:video_to_clip_u8)"""
     fs = getattr(model, "first_stage_model", None)
     if fs is None:
-        return None
+        return
     try:
         img = fs.decode(code_map)
     except RuntimeError:                                   # per-sample fallback on OOM, reference :77-82
         img = torch.cat([fs.decode(code_map[i:i + 1]) for i in range(code_map.shape[0])], 0)
-    return (torch.clamp(img, -0.5, 0.5) + 0.5)[:, :, :total_length, :, :]
+    log["samples"] = (torch.clamp(img, -0.5, 0.5) + 0.5)[:, :, :total_length, :, :]
+    if torch.is_tensor(samples_u8) or samples_u8:
+        from .frames import video_to_clip_u8
+        # a uint8 tensor is written in place (rows of a scripts_common.ClipStore), anything else true asks for a clip of its own
+        log["samples_u8"] = video_to_clip_u8(img.contiguous(), T=min(int(total_length), img.shape[2]),
+                                             out=samples_u8 if torch.is_tensor(samples_u8) else None)
 
 
 @torch.no_grad()
 def bidirect_sample(model, batch_size, total_length, step_size, context_size, temperature=1.0, top_k=None, top_p=None,
                     frame_n_steps=8, vid_n_steps=8, frame_c_temp=4.5, vid_c_temp=4.5, no_phase=False,
-                    ctemp_schedule='linear', strategy='maskgit', bootstrap=0):
+                    ctemp_schedule='linear', strategy='maskgit', bootstrap=0, samples_u8=False):
     T, H, W = model.mask_sampler.shape[-3:]
     ratio = 0.25                                            # 4 video frames per latent frame, reference :29
     step = int(step_size * ratio)
@@ -66,9 +73,7 @@ def bidirect_sample(model, batch_size, total_length, step_size, context_size, te
     if code_map.shape[1] == 1:
         code_map = code_map.expand(-1, 4, H, W)
     log["code_maps"] = code_map
-    samples = _decode(model, code_map, total_length)
-    if samples is not None:
-        log["samples"] = samples
+    _decode(model, code_map, total_length, log, samples_u8)
     prob_map = final_probs if boot_probs is None else torch.where(final_probs < 0., boot_probs, final_probs)
     # log-probability of the chosen codes of the first window (the reference gathers with the whole code
     # map, which only type-checks when there was no continuation — the case of every shipped script)
@@ -83,7 +88,7 @@ def bidirect_sample(model, batch_size, total_length, step_size, context_size, te
 @torch.no_grad()
 def extrapolate(model, vq_input, total_length, step_size, context_size, temperature=1.0, top_k=None, top_p=None,
                 frame_n_steps=8, vid_n_steps=8, frame_c_temp=4.5, vid_c_temp=4.5, no_phase=False,
-                ctemp_schedule='linear', strategy='maskgit', bootstrap=0):
+                ctemp_schedule='linear', strategy='maskgit', bootstrap=0, samples_u8=False):
     B, T, H, W = vq_input.shape
     ratio = 0.25
     step = int(step_size * ratio)
@@ -108,15 +113,13 @@ def extrapolate(model, vq_input, total_length, step_size, context_size, temperat
         code_map.append(x[:, ctx:].clone())
     code_map = torch.cat(code_map, 1)
     log["code_maps"] = code_map
-    samples = _decode(model, code_map, total_length)
-    if samples is not None:
-        log["samples"] = samples
+    _decode(model, code_map, total_length, log, samples_u8)
     return log
 
 
 @torch.no_grad()
 def draft_and_revise_sample(model, batch_size, total_length, step_size, context_size, n_draft, draft_t, draft_k, draft_p, n_revise,
-                            revise_t, revise_k, revise_p, M, draft=None):
+                            revise_t, revise_k, revise_p, M, draft=None, samples_u8=False):
     """Counterpart of `sample` in reference draft_and_revise_videos.py:22-60: one draft-and-revise pass over a zero (or given
     draft) code map of `step_size / 4` latent frames, then the first stage's decode.  `draft` (array-like of token ids,
     e.g. the code map a `bidirect_sample` run saved) skips the draft phase, as the shipped scripts do (`--np_draft`)."""
@@ -132,7 +135,5 @@ def draft_and_revise_sample(model, batch_size, total_length, step_size, context_
     if code_map.shape[1] == 1:
         code_map = code_map.expand(-1, 4, H, W)
     log = {"class_label": torch.zeros(batch_size, 1, dtype=torch.long, device=dev), "code_maps": code_map}
-    samples = _decode(model, code_map, total_length)
-    if samples is not None:
-        log["samples"] = samples
+    _decode(model, code_map, total_length, log, samples_u8)
     return log

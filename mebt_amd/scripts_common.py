@@ -31,6 +31,12 @@ def add_common_args(parser):
     parser.add_argument('--no_np', action='store_true')
     parser.add_argument('--latest', action='store_true')
     parser.add_argument('-v', '--verbose', action='store_true')
+    parser.add_argument('--device_u8', action='store_true',
+                        help="make the uint8 clips of the .npy on the GPU (mebt_amd/frames.py:video_to_clip_u8) instead of moving float32 "
+                             "samples to the host: the same file, a quarter of the bytes over PCIe and no float copies in host memory")
+    parser.add_argument('--u8_store', default='auto', choices=['auto', 'device', 'host'],
+                        help="with --device_u8: where the uint8 clips wait for the writer (auto: in HBM when they take at most a "
+                             "quarter of the free device memory, else in pinned host memory)")
     parser.add_argument('--dtype', default=None, choices=['bf16', 'f32'], help="engine precision (default: MEBT_COMPUTE_DTYPE or bf16)")
     return parser
 
@@ -105,3 +111,98 @@ def write_outputs(args, save_np, all_data, all_code, resolution, codemap_limit=N
         n_total = data.shape[0]
         data = (data * 255).astype(np.uint8)[np.random.permutation(n_total)[:args.n_sample]]
         np.save(save_np, data)
+
+
+class ClipStore:
+    """the uint8 clips [n_total, T, H, W, 3] of one sampling run, preallocated and filled row block by row block from the decoded
+    batches (mebt_amd/frames.py:video_to_clip_u8) in place of the reference's list of float32 arrays on the host.
+      where='device': the buffer lives in HBM; `target(b)` is the view of the next b rows for the kernel to write (no copy).
+      where='host':   a pinned host buffer filled with `non_blocking` copies; one synchronisation before the first read.
+      where='auto':   'device' when the buffer takes at most a quarter of the free device memory (the sampler's workspace and the
+                      key / value cache need the rest: the rule of `data.packed_resident: auto`), else 'host'."""
+
+    AUTO_FRACTION = 0.25
+
+    def __init__(self, n_total, T, H, W, where="auto", device="cuda"):
+        import torch
+        if where not in ("auto", "device", "host"):
+            raise ValueError(f"ClipStore: where={where!r} (auto, device or host)")
+        self.shape = (int(n_total), int(T), int(H), int(W), 3)
+        self.nbytes = int(np.prod(self.shape))
+        if where == "auto":
+            where = self.placement(self.nbytes)
+        self.where = where
+        if where == "device":
+            self.buf = torch.empty(self.shape, dtype=torch.uint8, device=device)
+        else:
+            self.buf = torch.empty(self.shape, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        self.n = 0
+        self._pending = False
+
+    @classmethod
+    def placement(cls, nbytes):
+        """what where='auto' chooses for a store of `nbytes`"""
+        import torch
+        return "device" if torch.cuda.is_available() and nbytes <= cls.AUTO_FRACTION * torch.cuda.mem_get_info()[0] else "host"
+
+    def reset(self):
+        """empty the store for the next run; the buffer is kept"""
+        self.sync()
+        self.n = 0
+
+    def target(self, b):
+        """what a driver's `samples_u8=` gets for a batch of b clips: the next b rows (device), or True (host: a clip of its own)"""
+        if self.n + b > self.shape[0]:
+            raise ValueError(f"ClipStore: {self.n} + {b} clips exceed the {self.shape[0]} rows it was made for")
+        return self.buf[self.n:self.n + b] if self.where == "device" else True
+
+    def put(self, clip):
+        """append uint8 clips [b, T, H, W, 3] (a device or host tensor, or a numpy array); rows handed out by `target` are in place"""
+        import torch
+        clip = torch.as_tensor(clip)
+        b = int(clip.shape[0])
+        if clip.dtype != torch.uint8 or tuple(clip.shape[1:]) != self.shape[1:]:
+            raise ValueError(f"ClipStore: expected uint8 [b, {', '.join(map(str, self.shape[1:]))}], got {clip.dtype} {tuple(clip.shape)}")
+        rows = self.target(b)
+        if self.where == "device":
+            if clip.data_ptr() != rows.data_ptr():
+                rows.copy_(clip, non_blocking=True)
+        else:
+            self.buf[self.n:self.n + b].copy_(clip, non_blocking=True)
+            self._pending = self._pending or clip.is_cuda
+        self.n += b
+
+    def sync(self):
+        if self._pending:
+            import torch
+            torch.cuda.synchronize()
+            self._pending = False
+
+    def select(self, idx):
+        """rows `idx` (an integer numpy array) of the filled part, in that order: a device tensor or a host tensor, like the store"""
+        import torch
+        self.sync()
+        idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+        return self.buf[:self.n].index_select(0, idx.to(self.buf.device))
+
+
+def write_outputs_u8(args, save_np, store, all_code, codemap_limit=None, keep_np=True):
+    """`write_outputs` for clips that are already bytes in a ClipStore: the same `<save_np>_codemap.npy`, the same
+    `np.random.permutation(n_total)[:args.n_sample]` call at the same point, the same `<save_np>.npy` (not written with
+    keep_np=False).  Returns the selected clips uint8 [n, T, H, W, C], on the device when the store is (None without pixel samples)."""
+    os.makedirs(os.path.dirname(save_np), exist_ok=True)
+    if args.save_codemap:
+        print('saving code_map numpy file to %s...' % (save_np + '_codemap'))
+        code = np.concatenate(all_code, 0)
+        np.save(save_np + '_codemap', code if codemap_limit is None else code[:codemap_limit])
+    if not args.no_np:
+        if store is None or store.n == 0:
+            print('no first stage attached (vtokens model): no pixel samples to save, token ids only (--save_codemap)')
+            return None
+        n_total = store.n
+        data = store.select(np.random.permutation(n_total)[:args.n_sample])
+        if keep_np:
+            print('saving numpy file to %s...' % save_np)
+            np.save(save_np, data.cpu().numpy())
+        return data
+    return None

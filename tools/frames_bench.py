@@ -22,9 +22,20 @@
   step     with the pack at hand also `packed`: next(loader) + move + step from the resident pack, in the same rotation as the pixel
            and token steps; `packed_minus_pixel_ms` is the median of the paired differences, next to the pairs' spread
 
+  video_u8 the decoded-video -> uint8-clip kernel (csrc/frames/frames.hip: video_to_clip_kernel) on [16, 3, 16, 128, 128] and
+           [4, 3, 128, 128, 128] fp32, event-timed over `--reps` launches, against the host route it replaces on the same tensor
+           (`.cpu().numpy()`, `* 255`, `astype(uint8)`, transpose to [B, T, H, W, 3], wall clock around a synchronise); the two
+           alternate round by round and their bytes are compared once.  GB/s = fp32 bytes read + uint8 bytes written over the
+           kernel time; the host route's figure is its wall time only
+  evaluate_stage  one draft stage of `python -m mebt_amd.evaluate` against the two processes it replaces (`mebt_amd.sample`, then
+           `mebt_amd.measure_fvd` on its .npy) on a micro model (6 layers, 64 wide, 64 tokens, 16 frames of 32 x 32, 64 clips, the real
+           side read from a file of embeddings): wall seconds per route, alternating.  At this size process start, torch's import
+           and the three model loads are nearly all of it: it measures those fixed costs, not a sweep at the shipped geometry
+
 The transformer and the VQGAN have random weights (time does not depend on them); the PNGs are smooth random images.
 
 Usage:  python tools/frames_bench.py [--steps 10] [--warmup 3] [--reps 50] [--workers 8 16] [--no-step] [--no-loader] [--no-packed]
+        python tools/frames_bench.py --only-video-u8 [--no-evaluate]
 """
 import argparse
 import json
@@ -138,6 +149,108 @@ def bench_gather(reps, rounds=9, B=6, T=16, R=128):
                     "copy_GBps": round(nbytes / (mc * 1e-6) / 1e9, 1), "gather_GBps": round(nbytes / (mg * 1e-6) / 1e9, 1),
                     "note": "back-to-back launches into a preallocated output, each wrapper's host path included; the input stays in the Infinity Cache"})
     return out
+
+
+def bench_video_u8(B, Td, H, W, reps, rounds=5):
+    """the kernel and the host route on the same decoded tensor; the host route starts from the float `samples` the drivers log"""
+    g = torch.Generator(device=DEV).manual_seed(0)
+    x = (torch.rand(B, 3, Td, H, W, device=DEV, generator=g) - 0.5) * 1.3
+    samples = torch.clamp(x, -0.5, 0.5) + 0.5
+    out = F.video_to_clip_u8(x)
+
+    def kernel():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            F.video_to_clip_u8(x, out=out)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3                      # us per launch
+
+    def host():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        d = samples.cpu().numpy()
+        d = np.ascontiguousarray(np.transpose((d * 255).astype(np.uint8), (0, 2, 3, 4, 1)))
+        return (time.perf_counter() - t0) * 1e3, d                   # ms
+
+    assert np.array_equal(host()[1], out.cpu().numpy())              # the same bytes
+    kernel()
+    tk, th = [], []
+    for r in range(rounds):
+        if r % 2 == 0:
+            tk.append(kernel()); th.append(host()[0])
+        else:
+            th.append(host()[0]); tk.append(kernel())
+    nbytes = x.numel() * 4 + out.numel()
+    mk, mh = statistics.median(tk), statistics.median(th)
+    return {"bench": "video_u8", "shape": [B, 3, Td, H, W], "reps": reps, "rounds": rounds, "kernel_us_median": round(mk, 2),
+            "kernel_us_min_max": [round(min(tk), 2), round(max(tk), 2)], "MB_moved": round(nbytes / 1e6, 2),
+            "kernel_GBps": round(nbytes / (mk * 1e-6) / 1e9, 1), "host_route_ms_median": round(mh, 2),
+            "host_route_ms_min_max": [round(min(th), 2), round(max(th), 2)], "host_over_kernel": round(mh * 1e3 / mk, 1),
+            "float32_MB_over_pcie": round(x.numel() * 4 / 1e6, 2), "uint8_MB_kept": round(out.numel() / 1e6, 2)}
+
+
+def bench_evaluate_stage(rounds=2):
+    """wall time of one draft stage: `evaluate --stages draft --runs 0` against `sample` + `measure_fvd`, fresh processes each"""
+    import subprocess
+    from mebt_amd import presets
+    from mebt_amd.config import AttrDict
+    from mebt_amd.i3d import InceptionI3d
+    from mebt_amd.vqgan import VQGAN
+    root = tempfile.mkdtemp(prefix="evaluate_bench_")
+    try:
+        torch.manual_seed(0)
+        vq_args = presets.vqgan_args(n_hiddens=16, embedding_dim=64, n_codes=512, sequence_length=16, resolution=32)
+        torch.save({"state_dict": VQGAN(vq_args).state_dict(), "hyper_parameters": {"args": vq_args}}, os.path.join(root, "vq.ckpt"))
+        cfg = presets.tiny(vtokens=False)
+        p, m = cfg.model.params, cfg.model.mask.params
+        p.block_size, p.n_layer, p.n_head, p.n_embd, p.sos_emb, p.vocab_size, p.first_stage_vocab_size = 64, 6, 2, 64, 8, 512, 512
+        p.mode = ["latent_enc", "latent_self", "latent_enc", "latent_dec", "lt2l", "latent_dec"]
+        m.max_token, m.shape, m.budget = 64, [4, 4, 4], 64
+        cfg.model.vqvae = AttrDict(params=AttrDict(ckpt_path=os.path.join(root, "vq.ckpt")))
+        model = presets.build_model(cfg, compute_dtype="bf16")
+        torch.save({"state_dict": {k: v for k, v in model.state_dict().items() if not k.startswith("first_stage_model.")},
+                    "hyper_parameters": model.hparams, "global_step": 0, "epoch": 0}, os.path.join(root, "gpt.ckpt"))
+        torch.save(InceptionI3d(400, in_channels=3).state_dict(), os.path.join(root, "i3d.pt"))
+        np.save(os.path.join(root, "real_emb.npy"), np.random.RandomState(0).randn(64, 400).astype(np.float32))
+        sampling = ("--gpt_ckpt gpt.ckpt --batch_size 16 --n_sample 64 --total_length 16 --step_size 16 --context_size 16 --vid_n_steps 8 "
+                    "--vid_c_temp 2.0 --no_phase --dataset stl --resolution 32 --save_codemap").split()
+        scoring = "--n_sample 64 --sequence_length 16 --i3d_ckpt i3d.pt --real_embeddings real_emb.npy".split()
+        env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+
+        def py(*argv):
+            r = subprocess.run([sys.executable, "-m", *argv], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+            if r.returncode != 0:
+                raise SystemExit(f"{argv[0]} failed:\n{r.stdout[-2000:]}\n{r.stderr[-3000:]}")
+
+        def one():
+            t0 = time.perf_counter()
+            py("mebt_amd.evaluate", *sampling, *scoring, "--exp_name", "one", "--runs", "0", "--stages", "draft")
+            return time.perf_counter() - t0
+
+        def two():
+            t0 = time.perf_counter()
+            py("mebt_amd.sample", *sampling, "--exp_name", "two")
+            t1 = time.perf_counter()
+            py("mebt_amd.measure_fvd", *scoring, "--np_file",
+               "results/two/numpy_files_16/stl/VID_n_steps8_temp1.0_ctemp2.0linear_maskgit_cosine_no_phase_run0.npy")
+            return time.perf_counter() - t0, t1 - t0
+
+        one(), two()                                                  # warm the file cache and the code object cache
+        t_one, t_two, t_sample = [], [], []
+        for r in range(rounds):
+            if r % 2 == 0:
+                t_one.append(one()); a, b = two()
+            else:
+                a, b = two(); t_one.append(one())
+            t_two.append(a); t_sample.append(b)
+        return {"bench": "evaluate_stage", "model": "micro 6L d64 block 64, 16 x 32 x 32, 64 clips, batch 16, 8 steps", "rounds": rounds,
+                "evaluate_s": [round(v, 2) for v in t_one], "two_process_s": [round(v, 2) for v in t_two],
+                "of_which_sample_s": [round(v, 2) for v in t_sample],
+                "note": "fresh processes; at this size start-up, imports and model loads dominate both routes"}
+    finally:
+        shutil.rmtree(root)
 
 
 def smooth_frames(rs, n, H, W):
@@ -314,10 +427,19 @@ def main():
     ap.add_argument("--no-step", action="store_true")
     ap.add_argument("--no-loader", action="store_true")
     ap.add_argument("--no-packed", action="store_true")
+    ap.add_argument("--only-video-u8", action="store_true", help="the video_u8 and evaluate_stage legs alone")
+    ap.add_argument("--no-evaluate", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("frames_bench measures on the GPU: no device visible")
     print(json.dumps({"bench": "clocks", "when": "start", "rocm_smi": clocks()}), flush=True)
+    for shape in ((16, 16, 128, 128), (4, 128, 128, 128)):
+        print(json.dumps(bench_video_u8(*shape, args.reps)), flush=True)
+    if not args.no_evaluate:
+        print(json.dumps(bench_evaluate_stage()), flush=True)
+    if args.only_video_u8:
+        print(json.dumps({"bench": "clocks", "when": "end", "rocm_smi": clocks()}), flush=True)
+        return
     for shape in ((6, 16, 128, 128, 128), (6, 16, 240, 320, 128)):
         for u8 in (False, True):
             print(json.dumps(bench_ingest(*shape, args.reps, u8=u8)), flush=True)
