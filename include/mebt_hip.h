@@ -206,6 +206,12 @@ int mebt_op_layernorm_bwd(int32_t dtype, const void* x, const void* dy, const fl
 int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
                           int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
                           int32_t ldo, int32_t force_generic, mebt_stream_t stream);
+/* Tests only: the same forward with gathered keys / values, as the sampling loops' cache is read: key / value row r of sample b is row
+ * kidx[b * NK + r] of a buffer of `kidx_rows` rows per sample (k, v point at sample 0, row 0).  bf16 MFMA forward only, NK <= 8192;
+ * anything else (fp32, force_generic, another head size) is MEBT_STATUS_ESHAPE. */
+int mebt_op_attention_fwd_gather(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
+                                 int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
+                                 int32_t ldo, int32_t force_generic, const int32_t* kidx, int32_t kidx_rows, mebt_stream_t stream);
 int mebt_op_attention_bwd(int32_t dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
                           const void* d_o, void* dq, void* dk, void* dv, float* delta, int32_t B, int32_t H,
                           int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo,
@@ -450,6 +456,10 @@ void mebt_debug_attn_legacy(int32_t bits);
 /* Tests only: the block order of the MFMA attention grids.  For a 1-D grid of T = X * H * B workgroups (X row blocks, H heads), workgroup
  * t writes t to pos_to_id[(b * H + h) * X + x] for the (x, h, b) it takes; xcd = 1 the XCD-local order, 0 the linear one. */
 int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int32_t xcd, int32_t* pos_to_id, mebt_stream_t stream);
+/* Tests only: the form of the most recent bf16 MFMA attention forward.  Returns the number of such launches since the previous call;
+ * out[4] (or NULL) = {waves per group (4 or 8), ring stages, split (0 = none, 1 = two groups in anti-phase: attn_fwd_pp, 2 = two groups
+ * in phase), grid size}; all zero when there was none.  Process-wide and unsynchronised, like the other debug hooks. */
+int32_t mebt_debug_attn_last_launch(int32_t out[4]);
 /* Diagnostics (tools/wgrad_bench.py): every grouped weight-gradient launch uses this tile (128x128, 128x64, 64x128 or 64x64 with ring
  * 2-4; 256x128 with ring 2-3; a deeper ring is clamped) instead of the tuned / shipped choice, any other tile makes the launch fail with
  * MEBT_STATUS_EINVAL; tbm = 0 switches the override off. */

@@ -61,6 +61,7 @@ PROTOTYPES = {
     "mebt_op_layernorm_fwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mebt_op_layernorm_bwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mebt_op_attention_fwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp]),
+    "mebt_op_attention_fwd_gather": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp, c_i32, c_vp]),
     "mebt_op_attention_bwd": (c_i32, [c_i32] + [c_vp] * 10 + [c_i32] * 10 + [c_vp]),
     "mebt_op_embed_fwd": (c_i32, [c_i32] + [c_vp] * 10 + [c_i32] * 8 + [c_vp]),
     "mebt_op_sample": (c_i32, [c_vp, c_vp, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
@@ -104,6 +105,7 @@ PROTOTYPES = {
     "mebt_debug_attn_dropout": (None, [C.c_uint64, c_f32, c_vp]),
     "mebt_debug_attn_legacy": (None, [c_i32]),
     "mebt_debug_attn_block_order": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mebt_debug_attn_last_launch": (c_i32, [C.POINTER(c_i32)]),
     "mebt_gemm_autotune": (None, [c_i32]),
     "mebt_gemm_autotune_enabled": (c_i32, []),
     "mebt_gemm_tune_export": (c_i64, [C.c_char_p, c_i64]),

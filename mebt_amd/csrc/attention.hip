@@ -318,6 +318,7 @@ int launch_attn_bwd_mfma(const AttnParams& p, hipStream_t stream);
 static int launch_attn_fwd_mfma(const AttnParams&, hipStream_t) { return -1; }
 static int launch_attn_bwd_mfma(const AttnParams&, hipStream_t) { return -1; }
 int launch_attn_block_order_probe(int, int, int, int, int32_t*, hipStream_t) { mebt_set_error("built without the MFMA attention"); return MEBT_EINVAL; }
+extern "C" int32_t mebt_debug_attn_last_launch(int32_t out[4]) { if (out) out[0] = out[1] = out[2] = out[3] = 0; return 0; }
 #endif
 #ifdef MEBT_HAVE_ATTN_MFMA
 static int g_force_generic = 0;

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "kernels.h"
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -977,6 +978,22 @@ static int check_layout(const AttnParams& p) {
 // one stage is enough when the streamed side fits one chunk: two workgroups per CU
 static int lds_bytes(int streamed_rows) { return streamed_rows <= CHUNK ? STAGE_BYTES : ATTN_LDS; }
 
+// The forward form of the most recent launch, for the tests (mebt_debug_attn_last_launch): which kernel a shape really selected.
+static int g_fwd_launch_count = 0;
+static int32_t g_fwd_last_launch[4] = {0, 0, 0, 0};
+static void note_fwd_launch(int waves, int stages, int split, dim3 grid) {
+    ++g_fwd_launch_count;
+    const int32_t rec[4] = {waves, stages, split, (int32_t)grid.x};
+    memcpy(g_fwd_last_launch, rec, sizeof rec);
+}
+extern "C" int32_t mebt_debug_attn_last_launch(int32_t out[4]) {
+    const int n = g_fwd_launch_count;
+    if (out) memcpy(out, g_fwd_last_launch, sizeof g_fwd_last_launch);
+    g_fwd_launch_count = 0;
+    memset(g_fwd_last_launch, 0, sizeof g_fwd_last_launch);
+    return n;
+}
+
 int launch_attn_fwd_mfma(const AttnParams& p_in, hipStream_t stream) {
     AttnParams p = p_in;
     drop_mark_small(p.drop, (uint64_t)p.B * p.H * p.NQ * p.NK);
@@ -995,16 +1012,22 @@ int launch_attn_fwd_mfma(const AttnParams& p_in, hipStream_t stream) {
         const dim3 grid((p.NQ + 63) / 64 * p.H * p.B);
         // short key sets: two stages of 128 keys (64 KiB: two workgroups per CU); long ones: four stages, one workgroup per CU
         static const int split_on = [] { const char* e = getenv("MEBT_ATTN_FWD_SPLIT"); return e ? atoi(e) : 1; }();
-        if (p.NK <= 1024) hipLaunchKernelGGL((attn_fwd_mfma<4, 2>), grid, dim3(256), 2 * CHUNK_BYTES + xl, stream, p);
-        else if (split_on && (long)grid.x <= 256) {    // one workgroup per CU at most: a second group of waves per query block
+        if (p.NK <= 1024) {
+            hipLaunchKernelGGL((attn_fwd_mfma<4, 2>), grid, dim3(256), 2 * CHUNK_BYTES + xl, stream, p);
+            note_fwd_launch(4, 2, 0, grid);
+        } else if (split_on && (long)grid.x <= 256) {    // one workgroup per CU at most: a second group of waves per query block
             if (split_on == 2) hipLaunchKernelGGL((attn_fwd_mfma<4, 2, 2>), grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);   // both groups in phase (A/B)
             else hipLaunchKernelGGL(attn_fwd_pp, grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);
+            note_fwd_launch(4, 2, split_on == 2 ? 2 : 1, grid);
+        } else {
+            hipLaunchKernelGGL((attn_fwd_mfma<4, 4>), grid, dim3(256), 4 * CHUNK_BYTES + xl, stream, p);
+            note_fwd_launch(4, 4, 0, grid);
         }
-        else hipLaunchKernelGGL((attn_fwd_mfma<4, 4>), grid, dim3(256), 4 * CHUNK_BYTES + xl, stream, p);
     } else {
         const dim3 grid((p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS * p.H * p.B);
         if (p.NK <= CHUNK) hipLaunchKernelGGL((attn_fwd_mfma<8, 1>), grid, dim3(WAVES * 64), 2 * CHUNK_BYTES + xl, stream, p);
         else hipLaunchKernelGGL((attn_fwd_mfma<8, 2>), grid, dim3(WAVES * 64), 2 * 2 * CHUNK_BYTES + xl, stream, p);
+        note_fwd_launch(8, p.NK <= CHUNK ? 1 : 2, 0, grid);
     }
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;

@@ -119,9 +119,9 @@ extern "C" int mebt_debug_attn_block_order(int32_t T, int32_t X, int32_t H, int3
     return launch_attn_block_order_probe(T, X, H, xcd, pos_to_id, S(stream));
 }
 
-extern "C" int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
-                                     int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
-                                     int32_t ldo, int32_t force_generic, mebt_stream_t stream) {
+static int op_attention_fwd(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B, int32_t H, int32_t NQ,
+                            int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv, int32_t ldo, int32_t force_generic,
+                            const int32_t* kidx, int32_t kidx_rows, mebt_stream_t stream) {
     if (int rc = check_dtype(dtype)) return rc;
     if (!q || !o || (NK > 0 && (!k || !v))) { mebt_set_error("attention: null pointer"); return MEBT_EINVAL; }
     AttnParams p;
@@ -129,10 +129,24 @@ extern "C" int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k
     p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse; p.B = B; p.H = H; p.NQ = NQ; p.NK = NK; p.HD = HD;
     p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
     p.drop = g_op_attn_drop; p.dmask = g_op_attn_dmask;
+    p.kidx = kidx; p.kidx_rows = kidx_rows;
     mebt_attn_force_generic(force_generic);
     const int rc = launch_attn_fwd(p, dtype, S(stream));
     mebt_attn_force_generic(0);
     return rc;
+}
+extern "C" int mebt_op_attention_fwd(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
+                                     int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
+                                     int32_t ldo, int32_t force_generic, mebt_stream_t stream) {
+    return op_attention_fwd(dtype, q, k, v, o, lse, B, H, NQ, NK, HD, ldq, ldk, ldv, ldo, force_generic, nullptr, 0, stream);
+}
+// tests only: the forward with gathered keys / values (AttnParams::kidx), which otherwise only the cached sampling forward reaches
+extern "C" int mebt_op_attention_fwd_gather(int32_t dtype, const void* q, const void* k, const void* v, void* o, float* lse, int32_t B,
+                                            int32_t H, int32_t NQ, int32_t NK, int32_t HD, int32_t ldq, int32_t ldk, int32_t ldv,
+                                            int32_t ldo, int32_t force_generic, const int32_t* kidx, int32_t kidx_rows,
+                                            mebt_stream_t stream) {
+    if (!kidx || kidx_rows <= 0) { mebt_set_error("attention_fwd_gather: needs an index list and the row count of its buffer"); return MEBT_EINVAL; }
+    return op_attention_fwd(dtype, q, k, v, o, lse, B, H, NQ, NK, HD, ldq, ldk, ldv, ldo, force_generic, kidx, kidx_rows, stream);
 }
 
 extern "C" int mebt_op_attention_bwd(int32_t dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
