@@ -14,12 +14,12 @@
 // Both kernels are templates on the output element.  float: the clip above.  uint8_t (`mebt_op_frames_to_clip_u8`, the real side of
 // FVD): the resampled byte goes through a 256-entry uint8 table instead (the reference's `((video + 0.5) * 255).byte()`, built on the
 // host: mebt_amd/frames.py:byte_table) and is stored as the I3D path's clip [B, T, R, R, 3].  There a frame is R rows of R * 3 bytes
-// and a channel is just a column, so the vertical pass walks the tile's contiguous run of output bytes four at a time, from the
-// first dword boundary at or below the run's start: one dword store per lane, byte stores only at the two ragged ends.
+// and a channel is just a column, so the vertical pass writes the tile's contiguous run of output bytes a dword per lane (byte_run.h).
 #include <string>
 
 #include "../common.h"
 #include "../../../include/mebt_hip.h"
+#include "byte_run.h"
 
 namespace {
 
@@ -31,14 +31,29 @@ __device__ __forceinline__ int clip8(int acc) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-// the bytes of `v` (lowest first) belong at run[j, j + 4), of which [0, n) exists; run + j is dword aligned
-__device__ __forceinline__ void store_quad(uint8_t* run, int j, int n, uint32_t v) {
-    if (j >= 0 && j + 4 <= n) {
-        *reinterpret_cast<uint32_t*>(run + j) = v;
-        return;
-    }
-    for (int c = 0; c < 4; ++c)
-        if (j + c >= 0 && j + c < n) run[j + c] = (uint8_t)(v >> (8 * c));
+// one pass of Pillow's resampler for N adjacent bytes: a[c] = clip8(1 << 21 + sum over the m taps of w[k] * s[k * stride + c])
+template <int N>
+__device__ __forceinline__ void taps(const int32_t* w, int m, const uint8_t* s, int stride, int (&a)[N]) {
+    for (int c = 0; c < N; ++c) a[c] = 1 << 21;
+    for (int k = 0; k < m; ++k)
+        for (int c = 0; c < N; ++c) a[c] += w[k] * (int)s[k * stride + c];
+    for (int c = 0; c < N; ++c) a[c] = clip8(a[c]);
+}
+
+// the launch's 256-entry table staged in LDS, one entry per lane (FR_THREADS of them); the caller's barrier publishes it
+template <typename Out>
+__device__ __forceinline__ const Out* stage_table(const Out* __restrict__ lut) {
+    __shared__ Out lut_s[256];
+    lut_s[threadIdx.x] = lut[threadIdx.x];
+    return lut_s;
+}
+
+// pixel i of one frame of the float clip [B, 3, T, R, R]: channel c is the plane at o + c * cstride (cstride = T * R * R)
+template <typename Out>
+__device__ __forceinline__ void store_planes(Out* o, size_t cstride, size_t i, Out c0, Out c1, Out c2) {
+    o[i] = c0;
+    o[cstride + i] = c1;
+    o[2 * cstride + i] = c2;
 }
 
 template <typename Out>
@@ -47,11 +62,10 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t
                                                                    int K, int rows, int span, const Out* __restrict__ lut,
                                                                    const int32_t* __restrict__ slots, int Bout) {
     extern __shared__ uint8_t tmp[];          // [span][R][3] uint8: the horizontally resampled source rows
-    __shared__ Out lut_s[256];
     const int n = blockIdx.y, bl = n / T, t = n - bl * T;
     const int b = slots ? slots[bl] : bl;
     if (b < 0 || b >= Bout) return;           // uniform over the block
-    lut_s[threadIdx.x] = lut[threadIdx.x];
+    const Out* lut_s = stage_table(lut);
     const int32_t* xmin = tab;
     const int32_t* cnt = tab + R;
     const int32_t* kk = tab + 2 * R;
@@ -65,86 +79,50 @@ __global__ __launch_bounds__(FR_THREADS) void frames_resize_kernel(const uint8_t
     // horizontal pass: source rows [ybase, ybase + nrow) of the crop -> tmp
     for (int i = threadIdx.x; i < nrow * R; i += FR_THREADS) {
         const int row = i / R, x = i - row * R;
-        const uint8_t* p = src + ((size_t)(y0 + ybase + row) * Ws + x0 + xmin[x]) * 3;
-        const int32_t* w = kk + (size_t)x * K;
-        const int m = cnt[x];
-        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-        for (int k = 0; k < m; ++k) {
-            const int wk = w[k];
-            a0 += wk * (int)p[3 * k];
-            a1 += wk * (int)p[3 * k + 1];
-            a2 += wk * (int)p[3 * k + 2];
-        }
+        int a[3];
+        taps(kk + (size_t)x * K, cnt[x], src + ((size_t)(y0 + ybase + row) * Ws + x0 + xmin[x]) * 3, 3, a);
         uint8_t* d = tmp + row * R3 + x * 3;
-        d[0] = (uint8_t)clip8(a0);
-        d[1] = (uint8_t)clip8(a1);
-        d[2] = (uint8_t)clip8(a2);
+        d[0] = (uint8_t)a[0];
+        d[1] = (uint8_t)a[1];
+        d[2] = (uint8_t)a[2];
     }
     __syncthreads();
 
+    // vertical pass: the bytes a[0, N) of output row r from byte `col` of its R3, one walk over the row's taps in tmp
+    auto vpass = [&](int r, int col, auto& a) {
+        const int ym = xmin[r] - ybase;
+        taps(kk + (size_t)r * K, min(cnt[r], nrow - ym), tmp + ym * R3 + col, R3, a);
+    };
     const size_t plane = (size_t)R * R;
     if constexpr (sizeof(Out) == 1) {
-        // vertical pass over the tile's run of (r1 - r0 + 1) * R3 output bytes, then the byte table
+        // the tile's run of (r1 - r0 + 1) * R3 output bytes through the byte table
         uint8_t* run = out + (((size_t)b * T + t) * R + r0) * R3;
         const int nrun = (r1 - r0 + 1) * R3;
-        const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
-        for (int j = 4 * (int)threadIdx.x - mis; j < nrun; j += 4 * FR_THREADS) {
-            const int rr = max(j, 0) / R3, col = max(j, 0) - rr * R3;
-            uint32_t v = 0;
-            if (j >= 0 && j + 4 <= nrun && col + 4 <= R3) {       // four columns of one output row: one walk over its taps
-                const int r = r0 + rr;
-                const int ym = xmin[r] - ybase;
-                const int m = min(cnt[r], nrow - ym);
-                const int32_t* w = kk + (size_t)r * K;
-                const uint8_t* s = tmp + ym * R3 + col;
-                int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21, a3 = 1 << 21;
-                for (int k = 0; k < m; ++k) {
-                    const int wk = w[k];
-                    a0 += wk * (int)s[k * R3];
-                    a1 += wk * (int)s[k * R3 + 1];
-                    a2 += wk * (int)s[k * R3 + 2];
-                    a3 += wk * (int)s[k * R3 + 3];
-                }
-                v = (uint32_t)lut_s[clip8(a0)] | (uint32_t)lut_s[clip8(a1)] << 8 | (uint32_t)lut_s[clip8(a2)] << 16 |
-                    (uint32_t)lut_s[clip8(a3)] << 24;
-            } else {                                              // a row boundary or a ragged end of the run: byte by byte
-                for (int c = 0; c < 4; ++c) {
-                    const int jj = j + c;
-                    if (jj < 0 || jj >= nrun) continue;
-                    const int r = r0 + jj / R3, cc = jj % R3;
-                    const int ym = xmin[r] - ybase;
-                    const int m = min(cnt[r], nrow - ym);
-                    const int32_t* w = kk + (size_t)r * K;
-                    const uint8_t* s = tmp + ym * R3 + cc;
-                    int a = 1 << 21;
-                    for (int k = 0; k < m; ++k) a += w[k] * (int)s[k * R3];
-                    v |= (uint32_t)lut_s[clip8(a)] << (8 * c);
-                }
-            }
-            store_quad(run, j, nrun, v);
-        }
+        auto byte = [&](int jj) {
+            int a[1];
+            vpass(r0 + jj / R3, jj % R3, a);
+            return lut_s[a[0]];
+        };
+        // four columns of one output row in one walk; a dword across a row boundary goes byte by byte
+        auto quad = [&](int j, uint32_t& v) {
+            const int rr = j / R3, col = j - rr * R3;
+            if (col + 4 > R3) return false;
+            int a[4];
+            vpass(r0 + rr, col, a);
+            v = (uint32_t)lut_s[a[0]] | (uint32_t)lut_s[a[1]] << 8 | (uint32_t)lut_s[a[2]] << 16 | (uint32_t)lut_s[a[3]] << 24;
+            return true;
+        };
+        write_run(run, nrun, 0, nrun, 4 * (int)threadIdx.x - run_mis(run), 4 * FR_THREADS, quad, byte);
         return;
     }
-    // vertical pass: output rows [r0, r1] from tmp, then the normalisation table; lanes along W -> coalesced plane stores
+    // output rows [r0, r1] through the normalisation table; lanes along W -> coalesced plane stores
     Out* o = out + ((size_t)b * 3 * T + t) * plane;              // channel c at o + c * T * plane
     const int nout = (r1 - r0 + 1) * R;
     for (int i = threadIdx.x; i < nout; i += FR_THREADS) {
         const int rr = i / R, x = i - rr * R, r = r0 + rr;
-        const int ym = xmin[r] - ybase;
-        const int m = min(cnt[r], nrow - ym);
-        const int32_t* w = kk + (size_t)r * K;
-        const uint8_t* s = tmp + ym * R3 + x * 3;
-        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-        for (int k = 0; k < m; ++k) {
-            const int wk = w[k];
-            a0 += wk * (int)s[k * R3];
-            a1 += wk * (int)s[k * R3 + 1];
-            a2 += wk * (int)s[k * R3 + 2];
-        }
-        const size_t off = (size_t)r * R + x;
-        o[off] = lut_s[clip8(a0)];
-        o[(size_t)T * plane + off] = lut_s[clip8(a1)];
-        o[2 * (size_t)T * plane + off] = lut_s[clip8(a2)];
+        int a[3];
+        vpass(r, x * 3, a);
+        store_planes(o, (size_t)T * plane, (size_t)r * R + x, lut_s[a[0]], lut_s[a[1]], lut_s[a[2]]);
     }
 }
 
@@ -153,11 +131,10 @@ template <typename Out>
 __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* __restrict__ frames, Out* __restrict__ out, int T, int Hs,
                                                                  int Ws, int y0, int x0, int R, const Out* __restrict__ lut,
                                                                  const int32_t* __restrict__ slots, int Bout) {
-    __shared__ Out lut_s[256];
     const int n = blockIdx.y, bl = n / T, t = n - bl * T;
     const int b = slots ? slots[bl] : bl;
     if (b < 0 || b >= Bout) return;
-    lut_s[threadIdx.x] = lut[threadIdx.x];
+    const Out* lut_s = stage_table(lut);
     __syncthreads();
     const size_t plane = (size_t)R * R;
     const uint8_t* src = frames + (size_t)n * Hs * Ws * 3;
@@ -165,26 +142,20 @@ __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* 
         // the frame is one run of R rows of R3 bytes; source row y is the R3 bytes at src + ((y0 + y) * Ws + x0) * 3
         const int R3 = R * 3, nrun = R * R3;
         uint8_t* run = out + ((size_t)b * T + t) * nrun;
-        const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
-        for (int j = 4 * (int)(blockIdx.x * FR_THREADS + threadIdx.x) - mis; j < nrun; j += 4 * (int)gridDim.x * FR_THREADS) {
-            uint32_t v = 0;
-            for (int c = 0; c < 4; ++c) {
-                const int jj = j + c;
-                if (jj < 0 || jj >= nrun) continue;
-                const int y = jj / R3, col = jj - y * R3;
-                v |= (uint32_t)lut_s[src[((size_t)(y0 + y) * Ws + x0) * 3 + col]] << (8 * c);
-            }
-            store_quad(run, j, nrun, v);
-        }
+        auto byte = [&](int jj) {
+            const int y = jj / R3, col = jj - y * R3;
+            return lut_s[src[((size_t)(y0 + y) * Ws + x0) * 3 + col]];
+        };
+        // the source bytes of a dword share no alignment with it: every dword is put together from its bytes
+        write_run(run, nrun, 0, nrun, 4 * (int)(blockIdx.x * FR_THREADS + threadIdx.x) - run_mis(run), 4 * (int)gridDim.x * FR_THREADS,
+                  [](int, uint32_t&) { return false; }, byte);
         return;
     }
     Out* o = out + ((size_t)b * 3 * T + t) * plane;
     for (int i = blockIdx.x * FR_THREADS + threadIdx.x; i < R * R; i += gridDim.x * FR_THREADS) {
         const int y = i / R, x = i - y * R;
         const uint8_t* p = src + ((size_t)(y0 + y) * Ws + x0 + x) * 3;
-        o[i] = lut_s[p[0]];
-        o[(size_t)T * plane + i] = lut_s[p[1]];
-        o[2 * (size_t)T * plane + i] = lut_s[p[2]];
+        store_planes(o, (size_t)T * plane, (size_t)i, lut_s[p[0]], lut_s[p[1]], lut_s[p[2]]);
     }
 }
 
@@ -195,13 +166,10 @@ __global__ __launch_bounds__(FR_THREADS) void frames_copy_kernel(const uint8_t* 
 // most 15 bytes before and after it; the LDS copy keeps the global address' offset mod 16, so any pack pointer and any R work), then
 // read back a pixel (float: three planes, lanes along W) or a dword of the output run (uint8) per lane.  Every offset into the pack
 // is 64-bit; an id outside [0, F) writes nothing.
-constexpr int PK_CHUNK = 6144;              // 2048 pixels, or 1536 dwords of the uint8 run; a multiple of 3, 4 and 16
-
 template <typename Out>
 __global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* __restrict__ pack, int64_t F, const int64_t* __restrict__ ids,
                                                                  Out* __restrict__ out, int T, int R, int nchunk, const Out* __restrict__ lut) {
     __shared__ __attribute__((aligned(16))) uint8_t buf[PK_CHUNK + 16];
-    __shared__ Out lut_s[256];
     const int64_t n = blockIdx.x / nchunk;
     const int k = (int)(blockIdx.x - n * nchunk);
     const int64_t id = ids[n];
@@ -209,16 +177,12 @@ __global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* 
     const int tid = threadIdx.x;
     const int nrun = R * R * 3;
     const uint8_t* src = pack + (size_t)id * (size_t)nrun;
-    uint8_t* run = nullptr;
-    int mis = 0;
-    if constexpr (sizeof(Out) == 1) {
-        run = reinterpret_cast<uint8_t*>(out) + (size_t)n * (size_t)nrun;
-        mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
-    }
-    // this block's bytes of the frame: [c0, c1); the uint8 chunks are counted in dwords of the output run, which starts `mis` early
-    const int c0 = max(k * PK_CHUNK - mis, 0), c1 = min((k + 1) * PK_CHUNK - mis, nrun);
+    uint8_t* run = sizeof(Out) == 1 ? reinterpret_cast<uint8_t*>(out) + (size_t)n * (size_t)nrun : nullptr;
+    // this block's bytes of the frame: [c0, c1); the uint8 chunks are counted in dwords of the output run, which starts run_mis early
+    const RunChunk ch = run_chunk(k, run ? run_mis(run) : 0, nrun);
+    const int c0 = ch.c0, c1 = ch.c1;
     if (c0 >= c1) return;
-    lut_s[tid] = lut[tid];
+    const Out* lut_s = stage_table(lut);
     const uint8_t* a = src + c0;
     const int len = c1 - c0;
     const int sh = (int)(reinterpret_cast<uintptr_t>(a) & 15);           // buf[sh + j] = a[j]: a + j and buf + sh + j agree mod 16
@@ -233,17 +197,7 @@ __global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* 
     const int s0 = sh - c0;                   // buf[s0 + j] = byte j of the frame, c0 <= j < c1
 
     if constexpr (sizeof(Out) == 1) {
-        for (int j = k * PK_CHUNK - mis + 4 * tid; j < c1; j += 4 * FR_THREADS) {
-            uint32_t v = 0;
-            if (j >= c0 && j + 4 <= c1) {
-                const uint8_t* s = buf + s0 + j;
-                v = (uint32_t)lut_s[s[0]] | (uint32_t)lut_s[s[1]] << 8 | (uint32_t)lut_s[s[2]] << 16 | (uint32_t)lut_s[s[3]] << 24;
-            } else {                           // a ragged end of the run
-                for (int c = 0; c < 4; ++c)
-                    if (j + c >= c0 && j + c < c1) v |= (uint32_t)lut_s[buf[s0 + j + c]] << (8 * c);
-            }
-            store_quad(run, j, nrun, v);
-        }
+        write_run(run, nrun, c0, c1, ch.j0 + 4 * tid, 4 * FR_THREADS, [&](int j) { return lut_s[buf[s0 + j]]; });
         return;
     }
     const size_t plane = (size_t)R * R;
@@ -252,9 +206,7 @@ __global__ __launch_bounds__(FR_THREADS) void pack_gather_kernel(const uint8_t* 
     Out* o = out + ((size_t)b * 3 * T + t) * plane;                      // channel c at o + c * T * plane
     for (int p = c0 / 3 + tid; p < c1 / 3; p += FR_THREADS) {
         const uint8_t* s = buf + s0 + 3 * p;
-        o[p] = lut_s[s[0]];
-        o[(size_t)T * plane + p] = lut_s[s[1]];
-        o[2 * (size_t)T * plane + p] = lut_s[s[2]];
+        store_planes(o, (size_t)T * plane, (size_t)p, lut_s[s[0]], lut_s[s[1]], lut_s[s[2]]);
     }
 }
 
@@ -279,9 +231,9 @@ __global__ __launch_bounds__(FR_THREADS) void video_to_clip_kernel(const float* 
     const int tid = threadIdx.x;
     const int nrun = HW * 3;
     uint8_t* run = out + (size_t)n * (size_t)nrun;
-    const int mis = (int)(reinterpret_cast<uintptr_t>(run) & 3);
-    // this block's bytes of the frame: [c0, c1), counted in dwords of the output run, which starts `mis` early
-    const int c0 = max(k * PK_CHUNK - mis, 0), c1 = min((k + 1) * PK_CHUNK - mis, nrun);
+    // this block's bytes of the frame: [c0, c1), counted in dwords of the output run, which starts run_mis(run) early
+    const RunChunk ch = run_chunk(k, run_mis(run), nrun);
+    const int c0 = ch.c0, c1 = ch.c1;
     if (c0 >= c1) return;                                    // uniform over the block
     const int p0 = c0 / 3, p1 = (c1 + 2) / 3;                // the pixels those bytes belong to: at most PK_CHUNK / 3 + 2
     const size_t plane = (size_t)Td * (size_t)HW;            // channel c of frame t at in + ((b * 3 + c) * Td + t) * HW
@@ -294,17 +246,7 @@ __global__ __launch_bounds__(FR_THREADS) void video_to_clip_kernel(const float* 
     }
     __syncthreads();
     const int s0 = -3 * p0;                                  // buf[s0 + j] = byte j of the frame, c0 <= j < c1
-    for (int j = k * PK_CHUNK - mis + 4 * tid; j < c1; j += 4 * FR_THREADS) {
-        uint32_t v = 0;
-        if (j >= c0 && j + 4 <= c1) {
-            const uint8_t* s = buf + s0 + j;
-            v = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
-        } else {                               // a ragged end of the run
-            for (int c = 0; c < 4; ++c)
-                if (j + c >= c0 && j + c < c1) v |= (uint32_t)buf[s0 + j + c] << (8 * c);
-        }
-        store_quad(run, j, nrun, v);
-    }
+    write_run(run, nrun, c0, c1, ch.j0 + 4 * tid, 4 * FR_THREADS, [&](int j) { return buf[s0 + j]; });
 }
 
 hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
@@ -312,6 +254,16 @@ hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 int fail(const char* who, const char* what) {
     mebt_set_error((std::string(who) + ": " + what).c_str());
     return MEBT_EINVAL;
+}
+
+// grid of the two chunked kernels over `nframes` runs of nrun bytes: one block per (run, chunk); `out` as in run_chunks
+int chunk_grid(const char* who, long nrun, const void* out, long nframes, int* nchunk, unsigned* blocks) {
+    if (nrun > (1l << 30)) return fail(who, "frame too large");                            // a run's bytes are indexed in int
+    const long n = run_chunks(nrun, out);
+    if (nframes * n > (1l << 24)) return fail(who, "too many frames for one launch");      // grid.x * 256 threads stays below 2^32
+    *nchunk = (int)n;
+    *blocks = (unsigned)(nframes * n);
+    return MEBT_OK;
 }
 
 // argument checks and launch of both entries
@@ -347,15 +299,10 @@ int pack_launch(const char* who, const uint8_t* pack, int64_t F, const int64_t* 
                 mebt_stream_t stream) {
     if (!pack || !ids || !out || !lut) return fail(who, "null pointer");
     if (F < 1 || B < 1 || T < 1 || R < 1) return fail(who, "bad shape");
-    if ((long)R * R * 3 > (1l << 30)) return fail(who, "frame too large");       // a frame's bytes are indexed in int
-    // a uint8 run starts up to `slack` bytes after the dword boundary its chunks are counted from: every run shares out's offset when
-    // a frame is a whole number of dwords, else any offset occurs
-    const long nrun = (long)R * R * 3;
-    const long slack = sizeof(Out) == 1 ? (nrun % 4 ? 3 : (long)(reinterpret_cast<uintptr_t>(out) & 3)) : 0;
-    const long nchunk = (nrun + slack + PK_CHUNK - 1) / PK_CHUNK;
-    const long blocks = (long)B * T * nchunk;
-    if (blocks > (1l << 24)) return fail(who, "too many frames for one launch");      // grid.x * 256 threads stays below 2^32
-    hipLaunchKernelGGL(pack_gather_kernel<Out>, dim3((unsigned)blocks), dim3(FR_THREADS), 0, S(stream), pack, F, ids, out, T, R, (int)nchunk, lut);
+    int nchunk;
+    unsigned blocks;
+    if (int e = chunk_grid(who, (long)R * R * 3, sizeof(Out) == 1 ? out : nullptr, (long)B * T, &nchunk, &blocks)) return e;
+    hipLaunchKernelGGL(pack_gather_kernel<Out>, dim3(blocks), dim3(FR_THREADS), 0, S(stream), pack, F, ids, out, T, R, nchunk, lut);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -389,14 +336,10 @@ extern "C" int mebt_op_video_to_clip_u8(const float* in, uint8_t* out, int32_t B
     const char* who = "video_to_clip_u8";
     if (!in || !out) return fail(who, "null pointer");
     if (B < 1 || Td < 1 || T < 1 || T > Td || H < 1 || W < 1) return fail(who, "bad shape");
-    if ((long)H * W * 3 > (1l << 30)) return fail(who, "frame too large");         // a frame's bytes are indexed in int
-    // a run starts up to `slack` bytes after the dword boundary its chunks are counted from, as in pack_launch
-    const long nrun = (long)H * W * 3;
-    const long slack = nrun % 4 ? 3 : (long)(reinterpret_cast<uintptr_t>(out) & 3);
-    const long nchunk = (nrun + slack + PK_CHUNK - 1) / PK_CHUNK;
-    const long blocks = (long)B * T * nchunk;
-    if (blocks > (1l << 24)) return fail(who, "too many frames for one launch");
-    hipLaunchKernelGGL(video_to_clip_kernel, dim3((unsigned)blocks), dim3(FR_THREADS), 0, S(stream), in, out, Td, T, H * W, (int)nchunk);
+    int nchunk;
+    unsigned blocks;
+    if (int e = chunk_grid(who, (long)H * W * 3, out, (long)B * T, &nchunk, &blocks)) return e;
+    hipLaunchKernelGGL(video_to_clip_kernel, dim3(blocks), dim3(FR_THREADS), 0, S(stream), in, out, Td, T, H * W, nchunk);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

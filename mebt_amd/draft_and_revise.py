@@ -13,7 +13,8 @@ import os
 import numpy as np
 import torch
 
-from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs, write_outputs_u8, ClipStore
+from .scripts_common import (BatchSink, add_common_args, data_resolution, load_model, make_store, resolve_checkpoint, write_outputs,
+                             write_outputs_u8)
 
 
 def build_parser():
@@ -23,13 +24,19 @@ def build_parser():
     parser.add_argument('--draft_t', type=float, default=1.0)
     parser.add_argument('--draft_p', type=float, default=None)
     parser.add_argument('--draft_k', type=int, default=None)
+    add_revise_args(parser)
+    parser.add_argument('--np_draft', type=str, default=None)
+    parser.set_defaults(total_length=16)
+    return parser
+
+
+def add_revise_args(parser):
+    """the flags of the revise phase (mebt_amd/evaluate.py takes them too)"""
     parser.add_argument('--n_revise', type=int, default=8)
     parser.add_argument('--revise_t', type=float, default=1.0)
     parser.add_argument('--revise_p', type=float, default=None)
     parser.add_argument('--revise_k', type=int, default=None)
     parser.add_argument('--M', type=int, default=2)
-    parser.add_argument('--np_draft', type=str, default=None)
-    parser.set_defaults(total_length=16)
     return parser
 
 
@@ -78,56 +85,38 @@ def run(args, gpt, resolution, draft, postfix, store=None, keep_np=True):
     clips or None)."""
     from .sampling import draft_and_revise_sample
     save_dir, save_np = output_names(args, postfix)
-    print('generating and saving video to %s...' % save_dir)
-    os.makedirs(save_dir, exist_ok=True)
-    all_data, all_code = [], []
-    n_row = int(np.sqrt(args.batch_size))
     n_batch = args.n_sample // args.batch_size + min(1, args.n_sample % args.batch_size)       # :165
+    sink = BatchSink(args, save_dir, int(np.sqrt(args.batch_size)), n_batch, store)
     with torch.no_grad():
         for sample_id in range(n_batch):
             draft_batch = None if draft is None else draft[sample_id * args.batch_size:(sample_id + 1) * args.batch_size]
             bs = args.batch_size if draft_batch is None else len(draft_batch)
             if bs == 0:
                 break
-            u8 = dict(samples_u8=store.target(bs)) if store is not None else {}
             logs = draft_and_revise_sample(gpt, bs, total_length=args.total_length, step_size=args.step_size, context_size=args.context_size,
                                            n_draft=args.n_draft, draft_t=args.draft_t, draft_k=args.draft_k, draft_p=args.draft_p,
                                            n_revise=args.n_revise, revise_t=args.revise_t, revise_k=args.revise_k, revise_p=args.revise_p,
-                                           M=args.M, draft=draft_batch, **u8)
-            if "samples" in logs:
-                if args.save_videos and sample_id < args.save_n:
-                    save_video_grid(logs['samples'], os.path.join(save_dir, 'generation_%d.%s' % (sample_id, args.format)), n_row)
-                if store is not None:
-                    store.put(logs['samples_u8'])
-                else:
-                    all_data.append(logs['samples'].cpu().numpy())
-            all_code.append(logs['code_maps'].cpu().numpy())
-            if args.verbose:
-                print(f"batch {sample_id + 1}/{n_batch}: code map {tuple(logs['code_maps'].shape)}", flush=True)
+                                           M=args.M, draft=draft_batch, **sink.target(bs))
+            sink.put(sample_id, logs)
     if args.np_draft is not None:                                              # :185-187
         os.makedirs(os.path.dirname(save_np), exist_ok=True)
         with open(save_np + '.txt', 'w') as f:
             f.write(args.np_draft)
     if store is not None:
-        return save_np, write_outputs_u8(args, save_np, store, all_code, keep_np=keep_np)
-    write_outputs(args, save_np, all_data, all_code, resolution)
+        return save_np, write_outputs_u8(args, save_np, store, sink.all_code, keep_np=keep_np)
+    write_outputs(args, save_np, sink.all_data, sink.all_code, resolution)
     return save_np, None
 
 
 def main(argv=None):
-    from .config import load_config
     args, unknown = build_parser().parse_known_args(argv)
-    config = load_config(args.base, [u for u in unknown if "=" in u])
-    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+    resolution = data_resolution(args, unknown)
     resolve_checkpoint(args)
     print(args.gpt_ckpt)
     draft, postfix = apply_np_draft(args)
     os.makedirs(args.save, exist_ok=True)
     gpt = load_model(args)
-    store = None
-    if args.device_u8 and gpt.first_stage_model is not None and not args.no_np:
-        store = ClipStore(n_clips(args, draft), args.total_length, resolution, resolution, where=args.u8_store)
-    return run(args, gpt, resolution, draft, postfix, store)[0]
+    return run(args, gpt, resolution, draft, postfix, make_store(args, gpt, n_clips(args, draft), resolution))[0]
 
 
 if __name__ == "__main__":

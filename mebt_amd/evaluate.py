@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import draft_and_revise, measure_fvd, sample
-from .scripts_common import ClipStore, load_model, resolve_checkpoint
+from .scripts_common import ClipStore, data_resolution, load_model, resolve_checkpoint
 
 STAGES = ("draft", "revise")
 
@@ -68,23 +68,9 @@ def parse_stages(text):
 def build_parser():
     parser = sample.build_parser()
     parser.description = "sample, revise and score a checkpoint in one process (the sweep of the reference's scripts/valid_dnr_*.sh)"
-    # draft_and_revise.py: the revise phase (the draft phase is the sample stage's code map, as in the shipped scripts)
-    parser.add_argument('--n_revise', type=int, default=8)
-    parser.add_argument('--revise_t', type=float, default=1.0)
-    parser.add_argument('--revise_p', type=float, default=None)
-    parser.add_argument('--revise_k', type=int, default=None)
-    parser.add_argument('--M', type=int, default=2)
-    # measure_fvd.py
-    parser.add_argument('--n_neighbor', type=int, default=5)
-    parser.add_argument('--compute_fvd', action='store_true')
-    parser.add_argument('--train', action='store_true')
-    parser.add_argument('--sample_fake_n_frames', type=int, default=1)
-    parser.add_argument('--real_embeddings', type=str, default='',
-                        help='.npy of the real set\'s [N, 400] I3D logits: loaded if it exists, else computed and written')
-    parser.add_argument('--packed_path', type=str, default='')
-    parser.add_argument('--i3d_ckpt', type=str, default=None)
-    parser.add_argument('--i3d_dtype', type=str, default='f16', choices=['f16', 'f32'])
-    parser.add_argument('--i3d_batch', type=int, default=None)
+    # the revise phase (the draft phase is the sample stage's code map, as in the shipped scripts), then the scoring
+    draft_and_revise.add_revise_args(parser)
+    measure_fvd.add_scoring_args(parser)
     # the sweep
     parser.add_argument('--runs', type=parse_runs, default=parse_runs('0-9'), help="a range or a comma list, e.g. 0-9 or 0,3,4")
     parser.add_argument('--stages', type=parse_stages, default=list(STAGES), help="draft, revise or draft,revise")
@@ -141,11 +127,9 @@ def summary_path(args):
 
 
 def main(argv=None):
-    from .config import load_config
     from .fvd import frechet_distance, polynomial_mmd
     args, unknown = parse_args(argv)
-    config = load_config(args.base, [u for u in unknown if "=" in u])
-    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+    resolution = data_resolution(args, unknown)
     resolve_checkpoint(args)
     print(args.gpt_ckpt)
     os.makedirs(args.save, exist_ok=True)
@@ -157,9 +141,7 @@ def main(argv=None):
     i3d = measure_fvd.load_model(args, device)
     real = measure_fvd.real_embeddings(fvd_args(args, ''), i3d, device)
 
-    n_draft_clips = sample.n_clips(args)
-    n_revise_clips = (args.n_sample // args.batch_size + min(1, args.n_sample % args.batch_size)) * args.batch_size
-    n_rows = max(n_draft_clips if "draft" in args.stages else 0, n_revise_clips if "revise" in args.stages else 0)
+    n_rows = max(sample.n_clips(args) if "draft" in args.stages else 0, draft_and_revise.n_clips(args, None) if "revise" in args.stages else 0)
     store = ClipStore(n_rows, args.total_length, resolution, resolution, where=args.u8_store)
     print(f'clip store: {store.nbytes / 2 ** 20:.1f} MiB on the {store.where}')
 

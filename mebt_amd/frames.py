@@ -28,6 +28,7 @@ output as float32, and their writer makes bytes of it with numpy's float32 `* 25
 (`mebt_op_video_to_clip_u8`) writes those bytes from the decoded tensor on the device, in the same clip layout, so a sample never
 visits the host as floats; `video_u8_twin` is its numpy statement.
 """
+import functools
 import math
 
 import numpy as np
@@ -140,7 +141,23 @@ def video_u8_twin(video, T):
 
 
 # ---- device side ---------------------------------------------------------------------------------------------------------
-_plans = {}
+@functools.lru_cache(maxsize=None)
+def table(kind, device):
+    """the 256-entry table the kernels look a byte up in, "norm", "byte" or "identity", on `device`: uploaded once per device"""
+    return torch.from_numpy({"norm": norm_table, "byte": byte_table, "identity": lambda: np.arange(256, dtype=np.uint8)}[kind]()).to(device)
+
+
+def take_out(who, out, shape, dtype, device, any_batch=False):
+    """the `out=` of an entry point: None makes the tensor, anything else must be a contiguous `dtype` tensor of `shape` on `device`
+    (any_batch: of any size along the first axis)"""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    got = tuple(getattr(out, "shape", ()))
+    if (not torch.is_tensor(out) or out.dtype != dtype or got[any_batch:] != tuple(shape)[any_batch:] or len(got) != len(shape)
+            or out.device != device or not out.is_contiguous()):
+        raise ValueError(f"{who}: `out` must be contiguous {str(dtype).split('.')[-1]} [{'*, ' * any_batch}{', '.join(map(str, shape[any_batch:]))}] "
+                         f"on {device}, got {getattr(out, 'dtype', type(out))} {got} on {getattr(out, 'device', 'the host')}")
+    return out
 
 
 class _Plan:
@@ -168,21 +185,16 @@ class _Plan:
             self.K, self.rows, self.span = 0, 0, 0
             tab = np.zeros(1, np.int32)
         self.tab = torch.from_numpy(tab).to(device)
-        self.lut = torch.from_numpy(norm_table()).to(device)
-        self.byte_lut = torch.from_numpy(byte_table()).to(device)
 
 
+@functools.lru_cache(maxsize=None)
 def plan(Hs, Ws, R, device):
-    key = (int(Hs), int(Ws), int(R), torch.device(device))
-    p = _plans.get(key)
-    if p is None:
-        p = _plans[key] = _Plan(Hs, Ws, R, device)
-    return p
+    return _Plan(Hs, Ws, R, device)
 
 
 def _ingest(frames, R, out, slots, u8, lut=None):
     """argument checks and launch of both outputs: float32 [B, 3, T, R, R], or (u8) uint8 [B, T, R, R, 3]; `lut` replaces the
-    plan's 256-entry table of the output's dtype"""
+    256-entry table of the output's dtype (`table`: "byte" or "norm")"""
     if frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
         raise ValueError(f"frame ingest: expected uint8 [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_cuda:
@@ -191,21 +203,16 @@ def _ingest(frames, R, out, slots, u8, lut=None):
     B, T, Hs, Ws, _ = frames.shape
     p = plan(Hs, Ws, R, frames.device)
     dtype, shape = (torch.uint8, (T, R, R, 3)) if u8 else (torch.float32, (3, T, R, R))
-    if out is None:
-        if slots is not None:
-            raise ValueError("frame ingest: `slots` needs `out`")
-        out = torch.empty(B, *shape, device=frames.device, dtype=dtype)
-    else:
-        if out.dtype != dtype or not out.is_contiguous() or tuple(out.shape[1:]) != shape:
-            raise ValueError(f"frame ingest: `out` must be contiguous {str(dtype).split('.')[-1]} [*, {', '.join(map(str, shape))}], "
-                             f"got {tuple(out.shape)}")
-        if slots is None and out.shape[0] != B:
-            raise ValueError("frame ingest: `out` has another batch size and no `slots` were given")
+    if out is None and slots is not None:
+        raise ValueError("frame ingest: `slots` needs `out`")
+    out = take_out("frame ingest", out, (B,) + shape, dtype, frames.device, any_batch=True)
+    if slots is None and out.shape[0] != B:
+        raise ValueError("frame ingest: `out` has another batch size and no `slots` were given")
     if slots is not None:
         if slots.dtype != torch.int32 or slots.numel() != B or slots.device != frames.device:
             raise ValueError("frame ingest: `slots` must be int32 [B] on the frames' device")
     if lut is None:
-        lut = p.byte_lut if u8 else p.lut
+        lut = table("byte" if u8 else "norm", frames.device)
     elif lut.dtype != dtype or lut.numel() != 256 or lut.device != frames.device or not lut.is_contiguous():
         raise ValueError(f"frame ingest: `lut` must be contiguous {str(dtype).split('.')[-1]} [256] on the frames' device")
     if B == 0:
@@ -245,13 +252,7 @@ def video_to_clip_u8(video, T=None, out=None):
     T = Td if T is None else int(T)
     if not 1 <= T <= Td:
         raise ValueError(f"video_to_clip_u8: T = {T} outside [1, {Td}]")
-    shape = (B, T, H, W, 3)
-    if out is None:
-        out = torch.empty(shape, device=video.device, dtype=torch.uint8)
-    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != video.device
-          or not out.is_contiguous()):
-        raise ValueError(f"video_to_clip_u8: `out` must be contiguous uint8 {list(shape)} on the video's device, got "
-                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+    out = take_out("video_to_clip_u8", out, (B, T, H, W, 3), torch.uint8, video.device)
     if B * H * W == 0:
         return out
     _lib.check(_lib.load().mebt_op_video_to_clip_u8(_lib.ptr(video), _lib.ptr(out), B, Td, T, H, W, _lib.cur_stream()))
@@ -298,6 +299,14 @@ class RawVideoBatch:
         return self._ingest(True)
 
 
+def collate_rest(batch, items):
+    """the tail of both collates: every key of the items but `video`, stacked in batch order like the default collate"""
+    for k in items[0]:
+        if k != "video":
+            batch[k] = torch.utils.data.default_collate([it[k] for it in items])
+    return batch
+
+
 def collate_raw(items, resolution):
     """collate for FrameListDataset(raw=True) items: clips that share a source size are stacked together (one ingest
     launch per size); `indices` are stacked in batch order like the default collate"""
@@ -308,11 +317,7 @@ def collate_raw(items, resolution):
     out = []
     for key, slots in groups.items():
         out.append((torch.stack([items[i]["video"] for i in slots]), torch.tensor(slots, dtype=torch.int32)))
-    batch = {"video": RawVideoBatch(out, len(items), resolution)}
-    for k in items[0]:
-        if k != "video":
-            batch[k] = torch.utils.data.default_collate([it[k] for it in items])
-    return batch
+    return collate_rest({"video": RawVideoBatch(out, len(items), resolution)}, items)
 
 
 def to_device_video(x, device, non_blocking=True):

@@ -48,8 +48,13 @@ def build_parser(sliding=False):
     if sliding:
         parser.add_argument('--slide', type=int, default=8)
     parser.add_argument('--n_sample', type=int, default=512 if sliding else 2048)
-    parser.add_argument('--n_neighbor', type=int, default=5)
     parser.add_argument('--dataset', type=str, default='mshapes', choices=['mshapes', 'ucf101', 'sky', 'taichi', 'stl'])
+    return add_scoring_args(parser)
+
+
+def add_scoring_args(parser):
+    """the flags of the scoring itself: the real side, the I3D, the CSV's name (mebt_amd/evaluate.py takes them too)"""
+    parser.add_argument('--n_neighbor', type=int, default=5)
     parser.add_argument('--compute_fvd', action='store_true')
     parser.add_argument('--train', action='store_true')
     parser.add_argument('--sample_fake_n_frames', type=int, default=1)

@@ -137,15 +137,9 @@ def build_pack(data_path, out_dir, resolution, splits=("train", "test"), resize=
     return done
 
 
-_ident = {}
-
-
 def identity_table(device):
     """uint8 [256] identity on `device`: the ingest's byte table that leaves PIL's bytes as they are"""
-    device = torch.device(device)
-    if device not in _ident:
-        _ident[device] = torch.arange(256, dtype=torch.uint8).to(device)
-    return _ident[device]
+    return frames.table("identity", device)
 
 
 def gpu_resize(frames_u8, R, device="cuda"):
@@ -158,16 +152,6 @@ def gpu_resize(frames_u8, R, device="cuda"):
 
 
 # ---- the gather ------------------------------------------------------------------------------------------------------------
-_tables = {}
-
-
-def _table(device, u8):
-    key = (torch.device(device), u8)
-    if key not in _tables:
-        _tables[key] = torch.from_numpy(frames.byte_table() if u8 else frames.norm_table()).to(device)
-    return _tables[key]
-
-
 def _gather(pack, ids, R, u8, out=None):
     if pack.dtype != torch.uint8 or pack.dim() != 4 or pack.shape[-1] != 3 or pack.shape[1] != pack.shape[2]:
         raise ValueError(f"pack gather: expected a uint8 pack [F, R, R, 3], got {pack.dtype} {tuple(pack.shape)}")
@@ -182,15 +166,13 @@ def _gather(pack, ids, R, u8, out=None):
     ids = ids.contiguous()
     B, T = ids.shape
     shape, dtype = ((B, T, R, R, 3), torch.uint8) if u8 else ((B, 3, T, R, R), torch.float32)
-    if out is None:
-        out = torch.empty(shape, device=pack.device, dtype=dtype)
-    elif out.dtype != dtype or tuple(out.shape) != shape or out.device != pack.device or not out.is_contiguous():
-        raise ValueError(f"pack gather: `out` must be contiguous {str(dtype).split('.')[-1]} {list(shape)} on the pack's device")
+    out = frames.take_out("pack gather", out, shape, dtype, pack.device)
     if B * T == 0 or pack.shape[0] == 0:
         return out
     lib = _lib.load()
     _lib.check((lib.mebt_op_pack_to_clip_u8 if u8 else lib.mebt_op_pack_to_video)(
-        _lib.ptr(pack), int(pack.shape[0]), _lib.ptr(ids), _lib.ptr(out), B, T, R, _lib.ptr(_table(pack.device, u8)), _lib.cur_stream()))
+        _lib.ptr(pack), int(pack.shape[0]), _lib.ptr(ids), _lib.ptr(out), B, T, R, _lib.ptr(frames.table("byte" if u8 else "norm", pack.device)),
+        _lib.cur_stream()))
     return out
 
 
@@ -204,6 +186,12 @@ def pack_to_video(pack, ids, R, out=None):
 def pack_to_clip_u8(pack, ids, R, out=None):
     """the same rows as the uint8 clip [B, T, R, R, 3] of the FVD real side: what `frames.frames_to_clip_u8` makes of them"""
     return _gather(pack, ids, R, u8=True, out=out)
+
+
+def check_rows(ids, F):
+    """host-side range check of pack rows before a gather or a memmap read: the kernel leaves a row outside [0, F) unwritten"""
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= F):
+        raise IndexError(f"packed batch: frame rows {int(ids.min())}..{int(ids.max())} outside the pack's [0, {F})")
 
 
 class PackedVideoBatch(frames.RawVideoBatch):
@@ -234,9 +222,7 @@ class PackedVideoBatch(frames.RawVideoBatch):
                                 self.host_ids)
 
     def _ingest(self, u8):
-        F = int(self.pack.shape[0])
-        if self.host_ids.numel() and (int(self.host_ids.min()) < 0 or int(self.host_ids.max()) >= F):
-            raise IndexError(f"packed batch: frame rows {int(self.host_ids.min())}..{int(self.host_ids.max())} outside the pack's [0, {F})")
+        check_rows(self.host_ids, int(self.pack.shape[0]))
         return _gather(self.pack, self.ids, self.resolution, u8)
 
 
@@ -324,16 +310,10 @@ def collate_packed(items, pack, resident):
     if resident:
         video = PackedVideoBatch(pack.device_rows, ids, pack.resolution)
     else:
-        F = len(pack.rows)
-        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= F):
-            raise IndexError(f"packed batch: frame rows {int(ids.min())}..{int(ids.max())} outside the pack's [0, {F})")
+        check_rows(ids, len(pack.rows))
         rows = torch.from_numpy(pack.rows[ids.reshape(-1).numpy()])
         video = PackedVideoBatch(rows, torch.arange(ids.numel(), dtype=torch.int64).view_as(ids), pack.resolution)
-    batch = {"video": video}
-    for k in items[0]:
-        if k != "video":
-            batch[k] = torch.utils.data.default_collate([it[k] for it in items])
-    return batch
+    return frames.collate_rest({"video": video}, items)
 
 
 def choose_resident(pack, setting="auto", device=None):

@@ -14,7 +14,8 @@ import os
 import numpy as np
 import torch
 
-from .scripts_common import add_common_args, resolve_checkpoint, load_model, save_video_grid, write_outputs, write_outputs_u8, ClipStore
+from .scripts_common import (BatchSink, add_common_args, data_resolution, load_model, make_store, resolve_checkpoint, write_outputs,
+                             write_outputs_u8)
 
 
 def build_parser():
@@ -64,11 +65,8 @@ def run(args, gpt, resolution, store=None, keep_np=True):
     uint8 clips or None)."""
     from .sampling import bidirect_sample, extrapolate
     save_dir, save_np = output_names(args)
-    print('generating and saving video to %s...' % save_dir)
-    os.makedirs(save_dir, exist_ok=True)
-    all_data, all_code = [], []
-    n_row = min(int(np.sqrt(args.batch_size)), 4)
     n_batch = args.n_sample // args.batch_size + 1                              # :249
+    sink = BatchSink(args, save_dir, min(int(np.sqrt(args.batch_size)), 4), n_batch, store)
     kw = dict(total_length=args.total_length, step_size=args.step_size, context_size=args.context_size, temperature=args.temp,
               top_k=args.top_k, top_p=args.top_p, frame_n_steps=args.frame_n_steps, vid_n_steps=args.vid_n_steps,
               frame_c_temp=args.frame_c_temp, vid_c_temp=args.vid_c_temp, no_phase=args.no_phase, ctemp_schedule=args.ctemp_schedule,
@@ -77,45 +75,28 @@ def run(args, gpt, resolution, store=None, keep_np=True):
     with torch.no_grad():
         for sample_id in range(n_batch):
             if vq_np is None:
-                u8 = dict(samples_u8=store.target(args.batch_size)) if store is not None else {}
-                logs = bidirect_sample(gpt, args.batch_size, **kw, **u8)
+                logs = bidirect_sample(gpt, args.batch_size, **kw, **sink.target(args.batch_size))
             else:
                 vq_x = torch.as_tensor(vq_np[sample_id * args.batch_size:(sample_id + 1) * args.batch_size]).long().cuda()
                 if vq_x.shape[0] == 0:
                     break
-                u8 = dict(samples_u8=store.target(vq_x.shape[0])) if store is not None else {}
-                logs = extrapolate(gpt, vq_x, **kw, **u8)
-            if "samples" in logs:
-                if args.save_videos and sample_id < args.save_n:
-                    save_video_grid(logs['samples'], os.path.join(save_dir, 'generation_%d.%s' % (sample_id, args.format)), n_row,
-                                    fps=10 if vq_np is None else 30)
-                if store is not None:
-                    store.put(logs['samples_u8'])
-                else:
-                    all_data.append(logs['samples'].cpu().numpy())
-            all_code.append(logs['code_maps'].cpu().numpy())
-            if args.verbose:
-                print(f"batch {sample_id + 1}/{n_batch}: code map {tuple(logs['code_maps'].shape)}", flush=True)
+                logs = extrapolate(gpt, vq_x, **kw, **sink.target(vq_x.shape[0]))
+            sink.put(sample_id, logs, fps=10 if vq_np is None else 30)
     if store is not None:
-        return save_np, write_outputs_u8(args, save_np, store, all_code, codemap_limit=args.n_sample, keep_np=keep_np)
-    write_outputs(args, save_np, all_data, all_code, resolution, codemap_limit=args.n_sample)
+        return save_np, write_outputs_u8(args, save_np, store, sink.all_code, codemap_limit=args.n_sample, keep_np=keep_np)
+    write_outputs(args, save_np, sink.all_data, sink.all_code, resolution, codemap_limit=args.n_sample)
     return save_np, None
 
 
 def main(argv=None):
-    from .config import load_config
     args, unknown = build_parser().parse_known_args(argv)
-    config = load_config(args.base, [u for u in unknown if "=" in u])
-    resolution = config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+    resolution = data_resolution(args, unknown)
     resolve_checkpoint(args)
     print(args.gpt_ckpt)
     os.makedirs(args.save, exist_ok=True)
     gpt = load_model(args)
     gpt.mask_sampler.schedule = args.schedule                                   # :219
-    store = None
-    if args.device_u8 and gpt.first_stage_model is not None and not args.no_np:
-        store = ClipStore(n_clips(args), args.total_length, resolution, resolution, where=args.u8_store)
-    return run(args, gpt, resolution, store)[0]
+    return run(args, gpt, resolution, make_store(args, gpt, n_clips(args), resolution))[0]
 
 
 if __name__ == "__main__":

@@ -75,6 +75,14 @@ def load_model(args):
     return model.cuda().eval()
 
 
+def data_resolution(args, unknown):
+    """the resolution of the samples as the command lines take it (:195-199 / :101-105): `data.resolution` of the `--base` configs
+    (with the key=value overrides among the unknown flags) when they describe an image folder, else --resolution"""
+    from .config import load_config
+    config = load_config(args.base, [u for u in unknown if "=" in u])
+    return config.data.resolution if ("data" in config and config.data.get("image_folder", False)) else args.resolution
+
+
 def save_video_grid(video, fname, nrow=None, fps=10):
     """reference mebt/utils.py:149-171: [B, C, T, H, W] in [0, 1] -> one animated grid file"""
     from PIL import Image
@@ -93,14 +101,19 @@ def save_video_grid(video, fname, nrow=None, fps=10):
     print('saved videos to', fname)
 
 
-def write_outputs(args, save_np, all_data, all_code, resolution, codemap_limit=None):
-    """the tail of both scripts (:275-291 / :180-198): `<save_np>_codemap.npy` (token ids) and `<save_np>.npy` (uint8 videos
-    [n, T, H, W, C], a random subset of n_sample) — the video file only when a first stage produced pixel samples"""
+def write_codemap(args, save_np, all_code, codemap_limit=None):
+    """the first half of both writers: the directory of the outputs, and `<save_np>_codemap.npy` (token ids) with --save_codemap"""
     os.makedirs(os.path.dirname(save_np), exist_ok=True)
     if args.save_codemap:
         print('saving code_map numpy file to %s...' % (save_np + '_codemap'))
         code = np.concatenate(all_code, 0)
         np.save(save_np + '_codemap', code if codemap_limit is None else code[:codemap_limit])
+
+
+def write_outputs(args, save_np, all_data, all_code, resolution, codemap_limit=None):
+    """the tail of both scripts (:275-291 / :180-198): `<save_np>_codemap.npy` (token ids) and `<save_np>.npy` (uint8 videos
+    [n, T, H, W, C], a random subset of n_sample) — the video file only when a first stage produced pixel samples"""
+    write_codemap(args, save_np, all_code, codemap_limit)
     if not args.no_np:
         if not all_data:
             print('no first stage attached (vtokens model): no pixel samples to save, token ids only (--save_codemap)')
@@ -190,11 +203,7 @@ def write_outputs_u8(args, save_np, store, all_code, codemap_limit=None, keep_np
     """`write_outputs` for clips that are already bytes in a ClipStore: the same `<save_np>_codemap.npy`, the same
     `np.random.permutation(n_total)[:args.n_sample]` call at the same point, the same `<save_np>.npy` (not written with
     keep_np=False).  Returns the selected clips uint8 [n, T, H, W, C], on the device when the store is (None without pixel samples)."""
-    os.makedirs(os.path.dirname(save_np), exist_ok=True)
-    if args.save_codemap:
-        print('saving code_map numpy file to %s...' % (save_np + '_codemap'))
-        code = np.concatenate(all_code, 0)
-        np.save(save_np + '_codemap', code if codemap_limit is None else code[:codemap_limit])
+    write_codemap(args, save_np, all_code, codemap_limit)
     if not args.no_np:
         if store is None or store.n == 0:
             print('no first stage attached (vtokens model): no pixel samples to save, token ids only (--save_codemap)')
@@ -206,3 +215,38 @@ def write_outputs_u8(args, save_np, store, all_code, codemap_limit=None, keep_np
             np.save(save_np, data.cpu().numpy())
         return data
     return None
+
+
+def make_store(args, gpt, n_clips, resolution):
+    """--device_u8: the ClipStore for the `n_clips` clips of one run, when a first stage decodes pixel samples and the .npy is wanted"""
+    if args.device_u8 and gpt.first_stage_model is not None and not args.no_np:
+        return ClipStore(n_clips, args.total_length, resolution, resolution, where=args.u8_store)
+    return None
+
+
+class BatchSink:
+    """where both `run`s leave a batch's logs: the grids of the first --save_n batches (--save_videos) under `save_dir`, the pixel
+    samples as uint8 clips in `store` (without one: in `all_data` as float32 arrays on the host, like the reference), the code maps
+    in `all_code` and the --verbose line"""
+
+    def __init__(self, args, save_dir, n_row, n_batch, store=None):
+        self.args, self.save_dir, self.n_row, self.n_batch, self.store = args, save_dir, n_row, n_batch, store
+        self.all_data, self.all_code = [], []
+        print('generating and saving video to %s...' % save_dir)
+        os.makedirs(save_dir, exist_ok=True)
+
+    def target(self, b):
+        """the keyword a driver gets for a batch of b clips: `samples_u8=` the store's next rows, or nothing"""
+        return dict(samples_u8=self.store.target(b)) if self.store is not None else {}
+
+    def put(self, sample_id, logs, fps=10):
+        if "samples" in logs:
+            if self.args.save_videos and sample_id < self.args.save_n:
+                save_video_grid(logs['samples'], os.path.join(self.save_dir, 'generation_%d.%s' % (sample_id, self.args.format)), self.n_row, fps=fps)
+            if self.store is not None:
+                self.store.put(logs['samples_u8'])
+            else:
+                self.all_data.append(logs['samples'].cpu().numpy())
+        self.all_code.append(logs['code_maps'].cpu().numpy())
+        if self.args.verbose:
+            print(f"batch {sample_id + 1}/{self.n_batch}: code map {tuple(logs['code_maps'].shape)}", flush=True)

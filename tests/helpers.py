@@ -86,6 +86,36 @@ def closed_form_hook():
     return hook, state
 
 
+def write_tree(root):
+    """rewrite the fixture's PNG tree under `root` (PNG is lossless: the decoded frames equal the fixture bit for bit)"""
+    from PIL import Image
+    d = np.load(os.path.join(G, "frames", "frames_data.npz"))
+    off = 0
+    for name, shp in zip(d["names"], d["shapes"]):
+        n = int(np.prod(shp))
+        path = os.path.join(root, str(name))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        Image.fromarray(d["pixels"][off:off + n].reshape(shp)).save(path)
+        off += n
+    for lst in ("train", "test"):
+        names = [str(x) for x in d[f"{lst}_list"]]
+        for n in names:
+            if not n.endswith(".png"):
+                open(os.path.join(root, n), "w").write("{}")
+        with open(os.path.join(root, f"{lst}.txt"), "w") as f:
+            f.write("\n".join(os.path.join(root, n) for n in names) + "\n")
+    return d
+
+
+def tiny_vqgan(n_codes=16384):
+    """a seeded 3D-VQGAN for 4-frame clips at resolution 16 (the pixel-space training tests) and its args"""
+    from mebt_amd import presets
+    from mebt_amd.vqgan import VQGAN
+    torch.manual_seed(5)
+    args = presets.vqgan_args(n_hiddens=32, downsample=(2, 2, 2), embedding_dim=32, n_codes=n_codes, sequence_length=4, resolution=16)
+    return VQGAN(args), args
+
+
 def record_measured(name, value, gate, note=""):
     """Append a measured error figure and its gate to gpurun_out/parity_measured.txt (copied to profiles/ after a GPU run), so
     that drift of the bf16 bounds is visible from round to round (VERDICT r03 weak #2).  Never fails a test."""

@@ -10,7 +10,8 @@ import torch
 
 from mebt_amd import frames as F
 from mebt_amd import measure_fvd as M
-from tests.test_frames_host import CASES, write_tree
+from tests.helpers import write_tree
+from tests.test_frames_host import CASES
 
 CLIP_CASES = [c for c in CASES if c[1]["sequence_length"] > 0]
 SIZES = [(12, 16), (15, 10)]          # source sizes (h, w) of the generated trees: landscape and portrait, mixed in every batch

@@ -13,7 +13,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from mebt_amd import frames as F
-from tests.test_frames_host import CASES, write_tree
+from tests.helpers import tiny_vqgan, write_tree
+from tests.test_frames_host import CASES
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,14 +69,6 @@ def test_raw_batches_equal_the_reference_items(tree, tag, kw, train, seed):
     assert torch.equal(batch["indices"], torch.from_numpy(d[f"{tag}__indices"]))
 
 
-def _vqgan(n_codes=16384):
-    from mebt_amd import presets
-    from mebt_amd.vqgan import VQGAN
-    torch.manual_seed(5)
-    args = presets.vqgan_args(n_hiddens=32, downsample=(2, 2, 2), embedding_dim=32, n_codes=n_codes, sequence_length=4, resolution=16)
-    return VQGAN(args), args
-
-
 def _tiny_model(vq):
     from mebt_amd import presets
     torch.manual_seed(3)
@@ -99,7 +92,7 @@ def test_train_step_on_raw_frames_equals_the_token_step(tree):
     items = [ds[i] for i in range(len(ds))]
     batch = F.collate_raw(items, kw["resolution"])
     ref_video = torch.from_numpy(d[f"{tag}__video"].reshape(len(items), 3, 4, 16, 16)).to(DEV)
-    vq, _ = _vqgan()
+    vq, _ = tiny_vqgan()
     vq = vq.to(DEV).eval()
     vq.compute_dtype = "f32"
     ids_ref = vq.encode(ref_video)
@@ -132,7 +125,7 @@ def test_pixel_video_step_takes_the_float_contract(tree):
     """a float pixel video [B, 3, T, H, W] (the reference's batch) goes through encode_to_z in TrainLoop.step"""
     from mebt_amd.trainer import TrainLoop
     _, d = tree
-    vq, _ = _vqgan()
+    vq, _ = tiny_vqgan()
     vq = vq.to(DEV).eval()
     video = torch.from_numpy(d["s4r16__video"].reshape(5, 3, 4, 16, 16)).to(DEV)
     model = _tiny_model(vq).to(DEV).train()
@@ -146,7 +139,7 @@ def test_train_cli_on_a_frame_folder_and_resume(tree, tmp_path):
     import yaml
     from mebt_amd import presets
     root, _ = tree
-    vq, args = _vqgan()
+    vq, args = tiny_vqgan()
     ck = str(tmp_path / "vqgan.ckpt")
     torch.save({"state_dict": vq.state_dict(), "hyper_parameters": {"args": args}}, ck)
 

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 from mebt_amd import frames as F
 from mebt_amd import measure_fvd as M
 from mebt_amd import measure_sliding_fvd as MS
-from tests.test_frames_host import write_tree
+from tests.helpers import write_tree
 from tests.test_fvd_frames_host import CLIP_CASES, fvd_args, ref_bytes, reference_real_clips, seed, write_png_tree
 from tests.test_gpu_fvd import closed_form_sd
 
@@ -24,7 +24,10 @@ SENTINEL = 0xA5
                                        (1, 3, 128, 96, 128),       # upscale
                                        (4, 2, 9, 9, 31),           # square source, upscale
                                        (2, 3, 200, 150, 64),       # portrait
-                                       (2, 3, 16, 24, 16)])        # crop side == R: the copy kernel
+                                       (2, 3, 16, 24, 16),         # crop side == R: the copy kernel
+                                       (2, 3, 60, 80, 47),         # rows of 141 bytes: a tile's run of 2256 bytes starts off a dword
+                                                                   # boundary in every other frame and takes three passes of the lanes
+                                       (2, 3, 47, 47, 47)])        # the same odd frames of 6627 bytes through the copy kernel
 def test_u8_kernel_matches_the_twin(B, T, h, w, R):
     rs = np.random.RandomState(B * 1000 + R)
     a = rs.randint(0, 256, (B, T, h, w, 3)).astype(np.uint8)

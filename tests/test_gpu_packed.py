@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 from mebt_amd import frames as F
 from mebt_amd import packed as P
 from mebt_amd.config import AttrDict
-from tests.test_packed_host import CASES, RESOLUTIONS, _seed, twin_resize, write_tree
+from tests.helpers import tiny_vqgan, write_tree
+from tests.test_packed_host import CASES, RESOLUTIONS, _seed, twin_resize
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,10 +46,11 @@ def check_gather(pack, pack_np, ids_np):
     assert np.array_equal(clip.cpu().numpy(), F.byte_table()[rows])
 
 
-@pytest.mark.parametrize("B,T,R", [(3, 5, 16), (2, 3, 17), (4, 2, 31), (1, 1, 1), (2, 4, 128)])
+@pytest.mark.parametrize("B,T,R", [(3, 5, 16), (2, 3, 17), (4, 2, 31), (1, 1, 1), (2, 4, 128), (2, 3, 47)])
 def test_gather_matches_numpy(B, T, R):
     """R = 17 and 31: frames of 867 / 2883 bytes, so source frames start off every alignment and the uint8 runs off a dword
-    boundary; R = 1: a 3-byte frame; R = 128: eight chunks per frame"""
+    boundary; R = 1: a 3-byte frame; R = 128: eight chunks per frame; R = 47: frames of 6627 bytes, two chunks each and an odd
+    length, so the chunked uint8 runs start at every offset from a dword boundary"""
     pack_np = np.random.RandomState(R).randint(0, 256, (N_FRAMES, R, R, 3)).astype(np.uint8)
     pack = torch.from_numpy(pack_np).to(DEV)
     for ids in id_sets(B, T, N_FRAMES):
@@ -186,14 +188,6 @@ def test_loader_batches_equal_the_reference_items(tree, twin_packs, capsys, tag,
 
 
 # ---- python -m mebt_amd.train -------------------------------------------------------------------------------------------------
-def _vqgan(n_codes=16384):
-    from mebt_amd import presets
-    from mebt_amd.vqgan import VQGAN
-    torch.manual_seed(5)
-    args = presets.vqgan_args(n_hiddens=32, downsample=(2, 2, 2), embedding_dim=32, n_codes=n_codes, sequence_length=4, resolution=16)
-    return VQGAN(args), args
-
-
 def _plain(x):
     if isinstance(x, dict):
         return {k: _plain(v) for k, v in x.items()}
@@ -213,7 +207,7 @@ def test_train_cli_from_a_pack_equals_the_folder_run(tree, twin_packs, tmp_path)
     import yaml
     from mebt_amd import presets
     root, _ = tree
-    vq, args = _vqgan()
+    vq, args = tiny_vqgan()
     ck = str(tmp_path / "vqgan.ckpt")
     torch.save({"state_dict": vq.state_dict(), "hyper_parameters": {"args": args}}, ck)
     cfg = _plain(presets.tiny(vtokens=False))

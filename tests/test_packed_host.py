@@ -11,12 +11,12 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden", "frames")
 sys.path.insert(0, ROOT)
 
 from mebt_amd import frames as F  # noqa: E402
 from mebt_amd import packed as P  # noqa: E402
 from mebt_amd.config import AttrDict  # noqa: E402
+from tests.helpers import write_tree  # noqa: E402
 
 # tests/golden/frames/make_golden_frames.py:CASES
 CASES = [("s4r16", dict(sequence_length=4, resolution=16, sample_every_n_frames=1, latent_shape=[1, 4, 4]), True, 11),
@@ -24,27 +24,6 @@ CASES = [("s4r16", dict(sequence_length=4, resolution=16, sample_every_n_frames=
          ("whole", dict(sequence_length=-1, resolution=12, sample_every_n_frames=1, latent_shape=[2, 3]), True, 13),
          ("test_s4r10", dict(sequence_length=4, resolution=10, sample_every_n_frames=1, latent_shape=[4]), False, 14)]
 RESOLUTIONS = (16, 12, 10)
-
-
-def write_tree(root):
-    """rewrite the fixture's PNG tree under `root` (PNG is lossless: the decoded frames equal the fixture bit for bit)"""
-    from PIL import Image
-    d = np.load(os.path.join(GOLD, "frames_data.npz"))
-    off = 0
-    for name, shp in zip(d["names"], d["shapes"]):
-        n = int(np.prod(shp))
-        path = os.path.join(root, str(name))
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        Image.fromarray(d["pixels"][off:off + n].reshape(shp)).save(path)
-        off += n
-    for lst in ("train", "test"):
-        names = [str(x) for x in d[f"{lst}_list"]]
-        for n in names:
-            if not n.endswith(".png"):
-                open(os.path.join(root, n), "w").write("{}")
-        with open(os.path.join(root, f"{lst}.txt"), "w") as f:
-            f.write("\n".join(os.path.join(root, n) for n in names) + "\n")
-    return d
 
 
 def twin_resize(frames, R):
