@@ -2,11 +2,16 @@
 // No kernels here: this file sequences the launches of gemm.hip / attention*.hip / elementwise.hip
 // on the caller's stream, carving every activation out of the caller-provided workspace.
 //
+// The one thing here that is specific to this model is how a block's mode routes the three token streams (latents S, contexts C,
+// targets T).  That is the table of route.h; the workspace layout, the LN1 jobs of forward and backward, the streams a block
+// rewrites and the blocks the loss reaches are derived from it, and the per-stream state below is indexed by stream id.
+//
 // Reference being replaced: embed (mebt/transformer.py:255-277), GPT.forward / Block.forward
 // (mebt/modules/gpt.py:159-195,234-253), shared_step loss (transformer.py:717-732), the autograd
 // backward of all of it, and AdamW (transformer.py:790-797).
 #include "common.h"
 #include "kernels.h"
+#include "route.h"
 #include "../../include/mebt_hip.h"
 #include <string.h>
 #include <math.h>
@@ -15,6 +20,11 @@
 #include <cstdlib>
 
 namespace {
+
+static_assert(RT_MAXJ <= MEBT_LN_MAXJ, "the LN1 jobs of a block go out in one launch");
+// the stream gradients in the order the workspace holds them and the embedding dropout visits them
+constexpr int GRAD_ORDER[RT_STREAMS] = {RT_S, RT_T, RT_C};
+const uint32_t EMB_SITE[RT_STREAMS] = {SITE_EMB_SOS, SITE_EMB_CTX, SITE_EMB_TGT};     // self.drop on the three inputs (gpt.py:238-240)
 
 struct LayerOffsets {
     // W flat (elements)
@@ -37,9 +47,8 @@ struct LayerAct {   // saved activations of one block
     void *qn, *kn, *q, *k, *v, *att, *x, *hn, *pre, *u, *out;
     float *mean1q, *rstd1q, *mean1k, *rstd1k, *mean2, *rstd2, *lse;
     uint16_t* dmask = nullptr;   // attention-dropout keep bits written by the MFMA forward, read by its two backward kernels (AttnParams::dmask)
-    const void* q_in;   // LN1 input of the query side (previous stream value); maskgit: the contexts stream
-    const void* k_in;   // LN1 input of the key side (enc: contexts, dec: sos); lt2l uses S and T; maskgit: the targets stream
-    void *c_out, *t_out;   // maskgit: the block output split back into contiguous contexts / targets (gpt.py:191-192)
+    const void* in[RT_STREAMS];   // the stream values at block entry (the LN1 inputs)
+    void* split[2];     // a block that rewrites two streams (maskgit): its output split back into contiguous streams (gpt.py:191-192)
     int NQ, NK, ldqkv_q, ldqkv_k;
 };
 
@@ -49,9 +58,10 @@ struct FwdCtx {
     int B = 0, N = 0, NC = 0, NT = 0;
     const int64_t *x_ids = nullptr, *ci = nullptr, *ti = nullptr;
     int32_t* ci32 = nullptr;         // inference: int32 copy of `ci` (the gathering attention of the key / value cache)
-    void *sos0 = nullptr, *ctx = nullptr, *tgt0 = nullptr;
+    int len[RT_STREAMS] = {0, 0, 0};                 // rows per sample of each stream: n_latent, NC, NT
+    void* emb[RT_STREAMS] = {nullptr, nullptr, nullptr};           // the embedded inputs
     std::vector<LayerAct> L;
-    const void *S_final = nullptr, *T_final = nullptr;
+    const void* fin[RT_STREAMS] = {nullptr, nullptr, nullptr};     // the stream values: updated block by block, final after the forward
     void* hf = nullptr; float *meanf = nullptr, *rstdf = nullptr;
     float* logits_ws = nullptr;
     float *row_lse = nullptr, *row_loss = nullptr; int* row_rank = nullptr; double* loss_out = nullptr;
@@ -59,14 +69,14 @@ struct FwdCtx {
     bool dlogits_ready = false;      // mebt_loss_with_grad has already written x.dlogits for `dlogits_scale`
     float dlogits_scale = 0.f;
     // backward scratch
-    void *g_S = nullptr, *g_T = nullptr; float* g_C = nullptr;
-    void* g_cat = nullptr;     // maskgit: cat[g_C, g_T], the gradient of a block output that spans both streams
+    void* g[RT_STREAMS] = {nullptr, nullptr, nullptr};      // stream gradients; the contexts' is fp32 (every latent_enc block adds to it)
+    void* g_cat = nullptr;     // maskgit: cat[g[C], g[T]], the gradient of a block output that spans both streams
     void *dlogits = nullptr, *dhf = nullptr, *datt = nullptr;
     // per-layer backward scratch, two sets (layer parity): the side stream may still read layer i's
     // operands while the main stream already produces layer i-1's
     struct Scratch { void *d4, *dh, *dx, *dqkv_q, *dqkv_k, *dqn, *dkn, *dout_m, *dx_m; } sc[2];
     float* delta = nullptr;
-    bool gS_defined = false, gT_defined = false, gC_defined = false;
+    bool def[RT_STREAMS] = {false, false, false};           // g[s] holds a gradient (the loss depends on the stream at this depth)
     int doutm_ready = -1;      // block whose dropout-masked output gradient was already written by the LN1 backward above it
     int last_bwd_lo = -1;      // lowest block the previous mebt_backward_layers call finished (doutm_ready is only valid for a contiguous descent)
     bool drop_on = false; uint64_t drop_seed = 0;
@@ -295,16 +305,7 @@ extern "C" int mebt_model_create(const mebt_model_desc* desc, mebt_model** out) 
     m->n_w = w; m->n_p = p;
     // liveness: walk backwards from the head, which reads the targets stream only (gpt.py:247)
     m->live.assign(d.n_layer, 0);
-    bool gS = false, gT = true;
-    for (int i = d.n_layer - 1; i >= 0; --i) {
-        switch (d.modes[i]) {
-            case MEBT_MODE_LATENT_ENC: if (gS) { m->live[i] = 1; m->tok_live = true; } break;
-            case MEBT_MODE_LATENT_SELF: if (gS) m->live[i] = 1; break;
-            case MEBT_MODE_LT2L: if (gS) { m->live[i] = 1; gT = true; } break;
-            case MEBT_MODE_LATENT_DEC: if (gT) { m->live[i] = 1; gS = true; } break;
-            case MEBT_MODE_MASKGIT: m->live[i] = 1; m->tok_live = true; m->has_maskgit = true; break;   // gT is always defined here
-        }
-    }
+    route_liveness(d.modes, d.n_layer, m->live.data(), m->tok_live, m->has_maskgit);
     // MEBT_HOST_ONLY=1 (sanitizer / layout tests on machines without a GPU): the handle answers the host-side queries
     // (offset tables, workspace sizes, argument validation); anything that launches returns the HIP error of its first call
     static const bool host_only = [] { const char* e = getenv("MEBT_HOST_ONLY"); return e && e[0] == '1'; }();
@@ -366,17 +367,6 @@ extern "C" int mebt_model_sync_lowp(mebt_model* m, mebt_stream_t stream) {
 // ---------------------------------------------------------------------------------------------------
 // workspace
 // ---------------------------------------------------------------------------------------------------
-static void mode_shape(const mebt_model* m, int mode, int NC, int NT, int& NQ, int& NK) {
-    const int NS = m->d.n_latent;
-    switch (mode) {
-        case MEBT_MODE_LATENT_ENC: NQ = NS; NK = NC; break;
-        case MEBT_MODE_LATENT_SELF: NQ = NS; NK = NS; break;
-        case MEBT_MODE_LATENT_DEC: NQ = NT; NK = NS; break;
-        case MEBT_MODE_MASKGIT: NQ = NC + NT; NK = NC + NT; break;
-        default: NQ = NS; NK = NS + NT; break;
-    }
-}
-
 // Lays the workspace out; with c.base == nullptr only measures.  In inference (training == 0)
 // all per-layer buffers alias one layer-sized region and the stream outputs ping-pong.
 static void carve(const mebt_model* m, Carve& c, FwdCtx& x, int B, int NC, int NT, int training) {
@@ -390,35 +380,30 @@ static void carve(const mebt_model* m, Carve& c, FwdCtx& x, int B, int NC, int N
     } else {
         x.tune = {nullptr, 0, nullptr, 0};
     }
-    x.sos0 = c.take(B * NS * d * e);
-    x.ctx = c.take((int64_t)B * NC * d * e);
-    x.tgt0 = c.take((int64_t)B * NT * d * e);
+    const int len[RT_STREAMS] = {(int)NS, NC, NT};
+    for (int s = 0; s < RT_STREAMS; ++s) { x.len[s] = len[s]; x.emb[s] = c.take((int64_t)B * len[s] * d * e); }
     x.ci32 = training ? nullptr : (int32_t*)c.take((int64_t)B * NC * 4);
     x.L.assign(m->d.n_layer, LayerAct());
-    const int64_t layer_base = c.off;
     int64_t layer_max = c.off;
-    void* pingS[2] = {nullptr, nullptr};
-    void* pingT[2] = {nullptr, nullptr};
-    if (!training) {
-        pingS[0] = c.take(B * NS * d * e); pingS[1] = c.take(B * NS * d * e);
-        pingT[0] = c.take((int64_t)B * NT * d * e); pingT[1] = c.take((int64_t)B * NT * d * e);
+    void* ping[RT_STREAMS][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    int n_ping[RT_STREAMS] = {0, 0, 0};
+    if (!training)
+        for (int s : {RT_S, RT_T})      // the streams a block can rewrite alone
+            for (int k = 0; k < 2; ++k) ping[s][k] = c.take((int64_t)B * len[s] * d * e);
+    for (int i = 0; i < m->d.n_layer; ++i) {    // a block that rewrites two streams: its split outputs outlive the per-layer region
+        const Route& r = route_of(m->d.modes[i]);
+        for (int j = 0; j < 2 && r.nq() == 2; ++j) x.L[i].split[j] = c.take((int64_t)B * len[r.q[j]] * d * e);
     }
-    for (int i = 0; i < m->d.n_layer; ++i)      // a maskgit block rewrites both streams: its split outputs outlive the per-layer region
-        if (m->d.modes[i] == MEBT_MODE_MASKGIT) {
-            x.L[i].c_out = c.take((int64_t)B * NC * d * e);
-            x.L[i].t_out = c.take((int64_t)B * NT * d * e);
-        }
     const int64_t after_ping = c.off;
-    int nS = 0, nT = 0;
     for (int i = 0; i < m->d.n_layer; ++i) {
         LayerAct& a = x.L[i];
-        const int mode = m->d.modes[i];
-        mode_shape(m, mode, NC, NT, a.NQ, a.NK);
+        const Route& r = route_of(m->d.modes[i]);
+        a.NQ = route_rows(r.q, len); a.NK = route_rows(r.k, len);
         const int64_t Mq = (int64_t)B * a.NQ, Mk = (int64_t)B * a.NK;
         if (!training) c.off = after_ping;
         a.qn = c.take(Mq * d * e);
         a.mean1q = (float*)c.take(Mq * 4); a.rstd1q = (float*)c.take(Mq * 4);
-        if (mode == MEBT_MODE_LATENT_SELF || mode == MEBT_MODE_MASKGIT) {
+        if (r.self) {
             a.kn = a.qn; a.mean1k = a.mean1q; a.rstd1k = a.rstd1q;
             a.q = c.take(Mq * 3 * d * e);
             a.k = (char*)a.q + d * e; a.v = (char*)a.q + 2 * d * e;
@@ -439,11 +424,10 @@ static void carve(const mebt_model* m, Carve& c, FwdCtx& x, int B, int NC, int N
         a.hn = c.take(Mq * d * e);
         a.pre = training ? c.take(Mq * 4 * d * e) : nullptr;
         a.u = c.take(Mq * 4 * d * e);
-        if (training || mode == MEBT_MODE_MASKGIT) a.out = c.take(Mq * d * e);
-        else a.out = (mode == MEBT_MODE_LATENT_DEC) ? pingT[(nT++) & 1] : pingS[(nS++) & 1];
+        if (training || r.nq() == 2) a.out = c.take(Mq * d * e);
+        else a.out = ping[r.q[0]][(n_ping[r.q[0]]++) & 1];
         if (c.off > layer_max) layer_max = c.off;
     }
-    (void)layer_base;
     c.off = layer_max;
     const int64_t R = (int64_t)B * NT;
     x.hf = c.take(R * d * e);
@@ -456,9 +440,7 @@ static void carve(const mebt_model* m, Carve& c, FwdCtx& x, int B, int NC, int N
         if ((int64_t)B * NC > Mmax) Mmax = (int64_t)B * NC;
         if (m->has_maskgit && (int64_t)B * (NC + NT) > Mmax) Mmax = (int64_t)B * (NC + NT);
         x.g_cat = m->has_maskgit ? c.take((int64_t)B * (NC + NT) * d * e) : nullptr;
-        x.g_S = c.take(B * NS * d * e);
-        x.g_T = c.take(R * d * e);
-        x.g_C = (float*)c.take((int64_t)B * NC * d * 4);
+        for (int s : GRAD_ORDER) x.g[s] = c.take((int64_t)B * len[s] * d * (s == RT_C ? 4 : e));
         x.dlogits = c.take(R * V * e);
         x.dhf = c.take(R * d * e);
         x.datt = c.take(Mmax * d * e);
@@ -499,12 +481,23 @@ static GemmParams gp(const void* A, const void* Bm, void* C, int M, int N, int K
     return p;
 }
 
-static int ln_fwd(const mebt_model* m, const void* x, void* y, int64_t gw, int64_t gb, float* mean, float* rstd, int rows,
-                  int seg, int seg_stride, int seg_off, hipStream_t st) {
+// LayerNorm with the affine parameters at P + gw / P + gb; seg / seg_stride / seg_off: LnFwdParams (kernels.h)
+static LnFwdParams ln_fwd_params(const mebt_model* m, const void* x, void* y, int64_t gw, int64_t gb, float* mean, float* rstd, int rows,
+                                 int seg = 0, int seg_stride = 0, int seg_off = 0) {
     LnFwdParams p;
     p.x = x; p.y = y; p.gamma = m->P + gw; p.beta = m->P + gb; p.mean = mean; p.rstd = rstd;
     p.rows = rows; p.d = m->d.n_embd; p.seg = seg; p.seg_stride = seg_stride; p.seg_off = seg_off;
-    return launch_ln_fwd(p, m->d.dtype, st);
+    return p;
+}
+// the attention of block `a`, forward fields; backward adds its gradient pointers
+static AttnParams attn_params(const mebt_model* m, const LayerAct& a, int B, const DropCfg& drop, uint16_t* dmask) {
+    AttnParams ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.q = a.q; ap.k = a.k; ap.v = a.v; ap.o = a.att; ap.lse = a.lse;
+    ap.B = B; ap.H = m->d.n_head; ap.NQ = a.NQ; ap.NK = a.NK; ap.HD = m->d.n_embd / m->d.n_head;
+    ap.ldq = a.ldqkv_q; ap.ldk = a.ldqkv_k; ap.ldv = a.ldqkv_k; ap.ldo = m->d.n_embd;
+    ap.drop = drop; ap.dmask = dmask;
+    return ap;
 }
 
 #define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
@@ -597,22 +590,20 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
     const float p_emb = drop_on ? m->d.embd_pdrop : 0.f, p_res = drop_on ? m->d.resid_pdrop : 0.f, p_att = drop_on ? m->d.attn_pdrop : 0.f;
 
     if (embedded) {   // GPT.forward boundary (gpt.py:234): the caller hands over fp32 embeddings
-        void* dst[3] = {x.sos0, x.ctx, x.tgt0};
-        const size_t cnt[3] = {(size_t)B * NS * d, (size_t)B * NC * d, (size_t)B * NT * d};
-        for (int k = 0; k < 3; ++k) {
-            if (!cnt[k]) continue;
-            if (!embedded[k]) { mebt_set_error("forward: null embedded input"); return MEBT_EINVAL; }
-            if (dt == MEBT_BF16) RC(launch_cast_f32_to_bf16(embedded[k], dst[k], cnt[k], st));
-            else MEBT_HIP_CHECK(hipMemcpyAsync(dst[k], embedded[k], cnt[k] * 4, hipMemcpyDeviceToDevice, st));
-            static const uint32_t site[3] = {SITE_EMB_SOS, SITE_EMB_CTX, SITE_EMB_TGT};     // self.drop on the three inputs (gpt.py:238-240)
-            if (p_emb > 0.f) RC(launch_apply_dropout(dst[k], dst[k], cnt[k], dt == MEBT_F32, dt == MEBT_F32, make_drop(dropout_seed, site[k], p_emb), st));
+        for (int s = 0; s < RT_STREAMS; ++s) {
+            const size_t cnt = (size_t)B * x.len[s] * d;
+            if (!cnt) continue;
+            if (!embedded[s]) { mebt_set_error("forward: null embedded input"); return MEBT_EINVAL; }
+            if (dt == MEBT_BF16) RC(launch_cast_f32_to_bf16(embedded[s], x.emb[s], cnt, st));
+            else MEBT_HIP_CHECK(hipMemcpyAsync(x.emb[s], embedded[s], cnt * 4, hipMemcpyDeviceToDevice, st));
+            if (p_emb > 0.f) RC(launch_apply_dropout(x.emb[s], x.emb[s], cnt, dt == MEBT_F32, dt == MEBT_F32, make_drop(dropout_seed, EMB_SITE[s], p_emb), st));
         }
         x.x_ids = nullptr; x.ci = nullptr; x.ti = nullptr;
     } else {
         EmbedParams ep;
         ep.x_ids = x_ids; ep.ci = kvc ? kv->dirty : ci; ep.ti = ti;       // cached: only the re-projected positions are embedded as contexts
         ep.tok_emb = m->P + m->tok_emb; ep.pos_emb = m->P + m->pos_emb; ep.mask_emb = m->P + m->mask_emb; ep.sos_emb = m->P + m->sos_emb;
-        ep.sos = x.sos0; ep.ctx = x.ctx; ep.tgt = x.tgt0;
+        ep.sos = x.emb[RT_S]; ep.ctx = x.emb[RT_C]; ep.tgt = x.emb[RT_T];
         ep.B = B; ep.N = N; ep.NC = kvc ? ND : NC; ep.NT = NT; ep.NS = NS; ep.d = d; ep.vocab = V; ep.block_size = m->d.block_size;
         ep.drop = make_drop(dropout_seed, 0, p_emb);       // gpt.py:238-240
         ProfRec r;
@@ -625,9 +616,8 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
         if (g_prof_on) { (void)hipEventRecord(r.b, st); g_prof.push_back(r); }
     }
 
-    const void* Sv = x.sos0;
-    const void* Tv = x.tgt0;
-    const void* Cv = x.ctx;          // read-only unless the model has 'maskgit' blocks (gpt.py:191-192)
+    const void** sv = x.fin;         // the current value of each stream; the contexts are read-only unless the model has 'maskgit' blocks
+    for (int s = 0; s < RT_STREAMS; ++s) sv[s] = x.emb[s];
     if (kvc && m->has_maskgit) { mebt_set_error("forward_kvcache: 'maskgit' blocks rewrite the contexts"); return MEBT_EINVAL; }
     int enc_seen = 0;
     // keys / values of the cached blocks: gathered by the MFMA attention kernel through an int32 copy of `ci` (head size 64, at most
@@ -638,45 +628,26 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
     for (int i = 0; i < m->d.n_layer; ++i) {
         LayerAct& a = x.L[i];
         const LayerOffsets& o = m->lo[i];
-        const int mode = m->d.modes[i];
-        const bool kv_layer = kvc && mode == MEBT_MODE_LATENT_ENC;
+        const Route& r = route_of(m->d.modes[i]);
+        const bool enc = m->d.modes[i] == MEBT_MODE_LATENT_ENC, kv_layer = kvc && enc;    // the cache holds the latent_enc blocks' keys / values
         const int Mq = B * a.NQ, Mk = kv_layer ? B * ND : B * a.NK;       // cached: only the dirty positions are normalised and projected
         RC(fw_wait(m, i, st));                             // a bucket of Linear weights that starts at this block
-        a.q_in = (mode == MEBT_MODE_LATENT_DEC) ? Tv : (mode == MEBT_MODE_MASKGIT) ? Cv : Sv;
+        for (int s = 0; s < RT_STREAMS; ++s) a.in[s] = sv[s];
         // LN1 on query and key with the SAME parameters (gpt.py:180-181), then the projections
         // (gpt.py:126-128); the three [d,d] weights are adjacent in W so QKV / KV fuse.  The key side
         // is independent of the query side: both LayerNorms are one launch, both projections are one launch.
         {
             LnFwdParams lj[MEBT_LN_MAXJ];
-            int nj = 0;
-            auto job = [&](const void* xin, void* y, float* mean, float* rstd, int rows, int seg, int seg_stride, int seg_off) {
-                LnFwdParams& p = lj[nj++];
-                p.x = xin; p.y = y; p.gamma = m->P + o.ln1w; p.beta = m->P + o.ln1b; p.mean = mean; p.rstd = rstd;
-                p.rows = rows; p.d = d; p.seg = seg; p.seg_stride = seg_stride; p.seg_off = seg_off;
-            };
-            if (mode == MEBT_MODE_MASKGIT) {       // query = key = LN1(cat[contexts, targets]) (gpt.py:176-181)
-                a.k_in = Tv;
-                job(Cv, a.qn, a.mean1q, a.rstd1q, B * NC, NC, NC + NT, 0);
-                job(Tv, a.qn, a.mean1q, a.rstd1q, B * NT, NT, NC + NT, NC);
-            } else {
-                job(a.q_in, a.qn, a.mean1q, a.rstd1q, Mq, 0, 0, 0);
-            }
-            if (mode == MEBT_MODE_LATENT_ENC) {
-                a.k_in = Cv;
-                job(Cv, a.kn, a.mean1k, a.rstd1k, Mk, 0, 0, 0);
-            } else if (mode == MEBT_MODE_LATENT_DEC) {
-                a.k_in = Sv;
-                job(Sv, a.kn, a.mean1k, a.rstd1k, Mk, 0, 0, 0);
-            } else if (mode == MEBT_MODE_LT2L) {   // key = LN1(cat[sos, targets]) (gpt.py:175,181)
-                a.k_in = Tv;
-                job(Sv, a.kn, a.mean1k, a.rstd1k, B * NS, NS, NS + NT, 0);
-                job(Tv, a.kn, a.mean1k, a.rstd1k, B * NT, NT, NS + NT, NS);
-            } else if (mode == MEBT_MODE_LATENT_SELF) {
-                a.k_in = nullptr;
+            RouteSeg sg[RT_MAXJ];
+            const int nj = route_fwd_segs(r, x.len, sg);   // a side of two streams is their concatenation (gpt.py:175-181)
+            for (int j = 0; j < nj; ++j) {
+                const RouteSeg& g = sg[j];
+                lj[j] = ln_fwd_params(m, sv[g.stream], g.key ? a.kn : a.qn, o.ln1w, o.ln1b, g.key ? a.mean1k : a.mean1q, g.key ? a.rstd1k : a.rstd1q,
+                                      g.key && kv_layer ? B * ND : B * g.len, g.seg, g.stride, g.off);
             }
             RC(launch_ln_fwd_multi(lj, nj, dt, st));
         }
-        if (mode == MEBT_MODE_LATENT_SELF || mode == MEBT_MODE_MASKGIT) {
+        if (r.self) {
             GemmParams p = gp(a.qn, m->Wop(o.wq), a.q, Mq, 3 * d, d, d, d, 3 * d, 1, 1);
             p.bias = m->P + o.bq;
             set_pf(m, p, o.wp, (int64_t)d * d);
@@ -696,19 +667,13 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
                 if (!kv_gather) RC(launch_index_rows(cache, a.k, ci, B, NC, N, 2 * d * 2, 0, st));   // no gathering attention for this shape: contiguous copy
             }
         }
-        if (mode == MEBT_MODE_LATENT_ENC) ++enc_seen;
-        // softmax(q k^T / sqrt(hd)) v  (gpt.py:131-137)
-        AttnParams ap;
-        memset(&ap, 0, sizeof(ap));
-        ap.q = a.q; ap.k = a.k; ap.v = a.v; ap.o = a.att; ap.lse = a.lse;
-        ap.B = B; ap.H = H; ap.NQ = a.NQ; ap.NK = a.NK; ap.HD = d / H;
-        ap.ldq = a.ldqkv_q; ap.ldk = a.ldqkv_k; ap.ldv = a.ldqkv_k; ap.ldo = d;
+        enc_seen += enc;
+        // softmax(q k^T / sqrt(hd)) v  (gpt.py:131-137, attention dropout gpt.py:135)
+        AttnParams ap = attn_params(m, a, B, make_drop(dropout_seed, 16 * i + SITE_ATTN, p_att), (p_att > 0.f && training) ? a.dmask : nullptr);
         if (kv_layer && kv_gather) {       // the attention kernel reads the cache rows at `ci` itself (index list in LDS): no copy
             char* cache = (char*)kv->cache + (size_t)(enc_seen - 1) * B * N * (2 * d) * 2;
             ap.k = cache; ap.v = cache + (size_t)d * 2; ap.kidx = x.ci32; ap.kidx_rows = N;
         }
-        ap.drop = make_drop(dropout_seed, 16 * i + SITE_ATTN, p_att);   // gpt.py:135
-        ap.dmask = (p_att > 0.f && training) ? a.dmask : nullptr;
         RC(launch_attn_fwd(ap, dt, st));
         // x = LN1(query) + proj(att)   — residual on the NORMALISED query (gpt.py:180,184)
         {
@@ -719,7 +684,7 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
             RC(gemm(m, p, st));
         }
         // x = x + mlp(LN2(x))  (gpt.py:185, 150-155)
-        RC(ln_fwd(m, a.x, a.hn, o.ln2w, o.ln2b, a.mean2, a.rstd2, Mq, 0, 0, 0, st));
+        RC(launch_ln_fwd(ln_fwd_params(m, a.x, a.hn, o.ln2w, o.ln2b, a.mean2, a.rstd2, Mq), dt, st));
         {
             GemmParams p = gp(a.hn, m->Wop(o.w1), a.pre, Mq, 4 * d, d, d, d, 4 * d, 1, 1);
             p.bias = m->P + o.b1; p.epilogue = EPI_GELU; p.C2 = a.u;
@@ -735,17 +700,20 @@ static int forward_impl(mebt_model* m, void* ws, int64_t ws_bytes, int32_t B, in
             else set_pf(m, p, m->head_w, (int64_t)V * d);
             RC(gemm(m, p, st));
         }
-        if (mode == MEBT_MODE_LATENT_DEC) Tv = a.out;                    // gpt.py:187-192
-        else if (mode == MEBT_MODE_MASKGIT) {                            // contexts, targets = x[:, :NC], x[:, NC:]
+        // the output replaces the query's stream(s) (gpt.py:187-192); two of them: contexts, targets = x[:, :NC], x[:, NC:]
+        if (r.nq() == 1) sv[r.q[0]] = a.out;
+        else {
             const int f32 = dt == MEBT_F32;
-            RC(launch_copy_rows(a.out, a.c_out, (long)B * NC, d, f32, f32, NC, NC + NT, 0, 0, 0, 0, st));
-            RC(launch_copy_rows(a.out, a.t_out, (long)B * NT, d, f32, f32, NT, NC + NT, NC, 0, 0, 0, st));
-            Cv = a.c_out; Tv = a.t_out;
-        } else Sv = a.out;
+            for (int j = 0, off = 0; j < 2; ++j) {
+                const int s = r.q[j];
+                RC(launch_copy_rows(a.out, a.split[j], (long)B * x.len[s], d, f32, f32, x.len[s], a.NQ, off, 0, 0, 0, st));
+                sv[s] = a.split[j];
+                off += x.len[s];
+            }
+        }
     }
-    x.S_final = Sv; x.T_final = Tv;
     // logits = head(ln_f(targets))  (gpt.py:247-248; head has no bias)
-    RC(ln_fwd(m, Tv, x.hf, m->lnf_w, m->lnf_b, x.meanf, x.rstdf, B * NT, 0, 0, 0, st));
+    RC(launch_ln_fwd(ln_fwd_params(m, sv[RT_T], x.hf, m->lnf_w, m->lnf_b, x.meanf, x.rstdf, B * NT), dt, st));
     RC(fw_wait(m, m->d.n_layer, st));                      // the head weight
     {
         GemmParams p = gp(x.hf, m->Wop(m->head_w), logits, B * NT, V, d, d, d, V, 1, 1);
@@ -826,15 +794,18 @@ extern "C" int mebt_loss_with_grad(mebt_model* m, void* ws, const float* logits,
 // ---------------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------------
-static int ln_bwd(const mebt_model* m, const void* x, const void* dy, const void* dy2, int64_t gw, int64_t gb, const float* mean,
-                  const float* rstd, void* dx, int dx_f32, int acc, int rows, int seg, int seg_stride, int seg_off, hipStream_t st,
-                  const void* dx_add = nullptr) {
+// backward of the LayerNorm whose affine parameters are at P + gw / P + gb: dx (+)= LN'(dy + dy2) + dx_add (LnBwdParams, kernels.h)
+static LnBwdParams ln_bwd_params(const mebt_model* m, const void* x, const void* dy, const void* dy2, const void* dx_add, int64_t gw, int64_t gb,
+                                 const float* mean, const float* rstd, void* dx, int dx_f32, int acc, int rows, int seg = 0, int seg_stride = 0,
+                                 int seg_off = 0) {
     LnBwdParams p;
     p.x = x; p.dy = dy; p.dy2 = dy2; p.dx_add = dx_add; p.gamma = m->P + gw; p.mean = mean; p.rstd = rstd; p.dx = dx; p.dx_f32 = dx_f32;
     p.dx_accumulate = acc; p.dgamma = m->gP + gw; p.dbeta = m->gP + gb; p.rows = rows; p.d = m->d.n_embd;
     p.seg = seg; p.seg_stride = seg_stride; p.seg_off = seg_off;
-    return launch_ln_bwd(p, m->d.dtype, st);
+    return p;
 }
+// is the gradient of stream s kept in fp32?  (the contexts' always: every latent_enc block adds to it)
+static int g_f32(const mebt_model* m, int s) { return s == RT_C || m->d.dtype == MEBT_F32; }
 
 // dW[n_out,k_in] = dY^T X (reduction over tokens), into the fp32 gradient buffer
 static int wgrad(const mebt_model* m, const void* dY, int ld_dy, const void* X, int ld_x, int64_t w_off, int n_out, int k_in, int tokens, hipStream_t st) {
@@ -868,8 +839,8 @@ static int head_backward_common(mebt_model* m, hipStream_t st) {
     RC(wgrad(m, x.dlogits, V, x.hf, d, m->head_w, V, d, R, sd));
     RC(dgrad(m, x.dlogits, V, m->head_w, x.dhf, R, V, d, EPI_NONE, nullptr, 0, st, m->lo[m->d.n_layer - 1].w2, (int64_t)4 * d * d,
              &x.L[m->d.n_layer - 1], 1));
-    RC(ln_bwd(m, x.T_final, x.dhf, nullptr, m->lnf_w, m->lnf_b, x.meanf, x.rstdf, x.g_T, 0, 0, R, 0, 0, 0, st));
-    x.gT_defined = true; x.gS_defined = false; x.gC_defined = false; x.doutm_ready = -1; x.last_bwd_lo = m->d.n_layer;
+    RC(launch_ln_bwd(ln_bwd_params(m, x.fin[RT_T], x.dhf, nullptr, nullptr, m->lnf_w, m->lnf_b, x.meanf, x.rstdf, x.g[RT_T], 0, 0, R), m->d.dtype, st));
+    x.def[RT_S] = x.def[RT_C] = false; x.def[RT_T] = true; x.doutm_ready = -1; x.last_bwd_lo = m->d.n_layer;
     return join_side(m, st);
 }
 
@@ -1052,23 +1023,24 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
     FwdCtx& x = m->ctx;
     LayerAct& a = x.L[i];
     const LayerOffsets& o = m->lo[i];
-    const int mode = m->d.modes[i], d = m->d.n_embd, dt = m->d.dtype, B = x.B, NS = m->d.n_latent, NT = x.NT, H = m->d.n_head;
+    const Route& r = route_of(m->d.modes[i]);
+    const int d = m->d.n_embd, dt = m->d.dtype, B = x.B;
     const int Mq = B * a.NQ, Mk = B * a.NK;
-    const bool isdec = mode == MEBT_MODE_LATENT_DEC, ismg = mode == MEBT_MODE_MASKGIT;
-    if (ismg ? !(x.gT_defined || x.gC_defined) : isdec ? !x.gT_defined : !x.gS_defined) return MEBT_OK;   // the loss does not depend on this block
+    if (!x.def[r.q[0]] && !(r.nq() == 2 && x.def[r.q[1]])) return MEBT_OK;   // the loss does not depend on this block's output
     const bool side = m->use_side;
     hipStream_t sd = side ? m->side : st;          // leaves (dW, db, dLN-affine) go here
     FwdCtx::Scratch& sc = x.sc[i & 1];
     if (side) MEBT_HIP_CHECK(hipStreamWaitEvent(st, m->ev_layer[i & 1], 0));   // side readers of this scratch set (layer i+2) are done
-    const void* dout = isdec ? x.g_T : x.g_S;
+    const void* dout = x.g[r.q[0]];
     const int f32 = dt == MEBT_F32;
     const size_t esz = m->esz();
-    if (ismg) {      // the block output spans both streams: dout = cat[g_C (fp32 accumulator), g_T]
-        const int NC = x.NC;
-        if (x.gC_defined) RC(launch_copy_rows(x.g_C, x.g_cat, (long)B * NC, d, 1, f32, 0, 0, 0, NC, NC + NT, 0, st));
-        else if (NC > 0) MEBT_HIP_CHECK(hipMemset2DAsync(x.g_cat, (size_t)(NC + NT) * d * esz, 0, (size_t)NC * d * esz, B, st));
-        if (x.gT_defined) RC(launch_copy_rows(x.g_T, x.g_cat, (long)B * NT, d, f32, f32, 0, 0, 0, NT, NC + NT, NC, st));
-        else MEBT_HIP_CHECK(hipMemset2DAsync((char*)x.g_cat + (size_t)NC * d * esz, (size_t)(NC + NT) * d * esz, 0, (size_t)NT * d * esz, B, st));
+    if (r.nq() == 2) {      // the block output spans two streams: dout = cat of their gradients, zero where none is defined
+        for (int j = 0, off = 0; j < 2; ++j) {
+            const int s = r.q[j], n = x.len[s];
+            if (x.def[s]) RC(launch_copy_rows(x.g[s], x.g_cat, (long)B * n, d, g_f32(m, s), f32, 0, 0, 0, n, a.NQ, off, st));
+            else if (n > 0) MEBT_HIP_CHECK(hipMemset2DAsync((char*)x.g_cat + (size_t)off * d * esz, (size_t)a.NQ * d * esz, 0, (size_t)n * d * esz, B, st));
+            off += n;
+        }
         dout = x.g_cat;
     }
     const float p_res = x.drop_on ? m->d.resid_pdrop : 0.f, p_att = x.drop_on ? m->d.attn_pdrop : 0.f;
@@ -1091,10 +1063,7 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
     // projection branch reads (x = qn + dropout(att Wp^T + bp))
     const void* dproj = sc.dx;
     {
-        LnBwdParams p;
-        p.x = a.x; p.dy = sc.dh; p.dy2 = nullptr; p.dx_add = dout; p.gamma = m->P + o.ln2w; p.mean = a.mean2; p.rstd = a.rstd2;
-        p.dx = sc.dx; p.dx_f32 = f32; p.dx_accumulate = 0; p.dgamma = m->gP + o.ln2w; p.dbeta = m->gP + o.ln2b;
-        p.rows = Mq; p.d = d; p.seg = 0; p.seg_stride = 0; p.seg_off = 0;
+        LnBwdParams p = ln_bwd_params(m, a.x, sc.dh, nullptr, dout, o.ln2w, o.ln2b, a.mean2, a.rstd2, sc.dx, f32, 0, Mq);
         if (p_res > 0.f) {
             p.dx2 = sc.dx_m; p.drop2 = make_drop(x.drop_seed, 16 * i + SITE_PROJ, p_res);
             dproj = sc.dx_m;
@@ -1105,14 +1074,9 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
     lv.wgrad(dproj, d, a.att, d, m->gW + o.wp, d, d, Mq, m->gP + o.bp, bg);
     RC(dgrad(m, dproj, d, o.wp, x.datt, Mq, d, d, EPI_NONE, nullptr, 0, st, o.wq, 3 * dd));
     // attention backward
-    AttnParams ap;
-    memset(&ap, 0, sizeof(ap));
-    ap.q = a.q; ap.k = a.k; ap.v = a.v; ap.o = a.att; ap.lse = a.lse; ap.B = B; ap.H = H; ap.NQ = a.NQ; ap.NK = a.NK; ap.HD = d / H;
-    ap.ldq = a.ldqkv_q; ap.ldk = a.ldqkv_k; ap.ldv = a.ldqkv_k; ap.ldo = d;
+    AttnParams ap = attn_params(m, a, B, make_drop(x.drop_seed, 16 * i + SITE_ATTN, p_att), p_att > 0.f ? a.dmask : nullptr);
     ap.d_o = x.datt; ap.lddo = d; ap.delta = x.delta;
-    ap.drop = make_drop(x.drop_seed, 16 * i + SITE_ATTN, p_att);
-    ap.dmask = p_att > 0.f ? a.dmask : nullptr;
-    if (mode == MEBT_MODE_LATENT_SELF || ismg) {
+    if (r.self) {
         ap.dq = sc.dqkv_q; ap.dk = (char*)sc.dqkv_q + (size_t)d * esz; ap.dv = (char*)sc.dqkv_q + (size_t)2 * d * esz;
         ap.lddq = ap.lddk = ap.lddv = 3 * d;
     } else {
@@ -1120,30 +1084,11 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
         ap.dk = sc.dqkv_k; ap.dv = (char*)sc.dqkv_k + (size_t)d * esz; ap.lddk = ap.lddv = 2 * d;
     }
     RC(launch_attn_bwd(ap, dt, st));
-    // LN1 backward of the query and key sides: one launch (they share LN1's dgamma/dbeta)
-    LnBwdParams lj[MEBT_LN_MAXJ];
-    int nj = 0;
-    auto ln1 = [&](const void* xin, const void* dy, const void* dy2, const float* mean, const float* rstd, void* dxp, int dx_f32, int acc,
-                   int rows, int seg, int seg_stride, int seg_off) {
-        LnBwdParams& p = lj[nj++];
-        p.x = xin; p.dy = dy; p.dy2 = dy2; p.dx_add = nullptr; p.gamma = m->P + o.ln1w; p.mean = mean; p.rstd = rstd;
-        p.dx = dxp; p.dx_f32 = dx_f32 || f32; p.dx_accumulate = acc; p.dgamma = m->gP + o.ln1w; p.dbeta = m->gP + o.ln1b;
-        p.rows = rows; p.d = d; p.seg = seg; p.seg_stride = seg_stride; p.seg_off = seg_off;
-    };
-    if (mode == MEBT_MODE_LATENT_SELF || ismg) {
+    // the gradients of LN1(query) (sc.dqn) and, unless the key is the query, of LN1(key) (sc.dkn)
+    if (r.self) {
         lv.wgrad(sc.dqkv_q, 3 * d, a.qn, d, m->gW + o.wq, 3 * d, d, Mq, m->gP + o.bq, bg);
         RC(dgrad(m, sc.dqkv_q, 3 * d, o.wq, sc.dqn, Mq, 3 * d, d, EPI_RESID, sc.dx, d, st, i > 0 ? m->lo[i - 1].w2 : -1, 4 * dd,
                  i > 0 ? &x.L[i - 1] : nullptr, 1));   // + dx (residual on qn)
-        if (side) RC(fork_side(m, st));
-        RC(flush_or_park(m, lv, sd, side));
-        if (ismg) {      // LN1 rows [0,NC) of each sample came from the contexts stream, the rest from the targets stream
-            const int NC = x.NC;
-            ln1(a.q_in, sc.dqn, nullptr, a.mean1q, a.rstd1q, x.g_C, 1, 0, B * NC, NC, NC + NT, 0);
-            ln1(a.k_in, sc.dqn, nullptr, a.mean1q, a.rstd1q, x.g_T, 0, 0, B * NT, NT, NC + NT, NC);
-            x.gC_defined = NC > 0; x.gT_defined = true;
-        } else {
-            ln1(a.q_in, sc.dqn, nullptr, a.mean1q, a.rstd1q, x.g_S, 0, 0, Mq, 0, 0, 0);
-        }
     } else {
         lv.wgrad(sc.dqkv_q, d, a.qn, d, m->gW + o.wq, d, d, Mq, m->gP + o.bq, bg);
         lv.wgrad(sc.dqkv_k, 2 * d, a.kn, d, m->gW + o.wk, 2 * d, d, Mk, m->gP + o.bk, bg);
@@ -1158,31 +1103,27 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
             }
             if (Mk > 0) RC(gemm_pair(m, pk, pq, st)); else RC(gemm(m, pq, st));
         }
-        if (side) RC(fork_side(m, st));
-        RC(flush_or_park(m, lv, sd, side));
-        if (mode == MEBT_MODE_LATENT_ENC) {
-            ln1(a.q_in, sc.dqn, nullptr, a.mean1q, a.rstd1q, x.g_S, 0, 0, Mq, 0, 0, 0);
-            if (Mk > 0) {   // contexts feed every latent_enc block: accumulate in fp32
-                ln1(a.k_in, sc.dkn, nullptr, a.mean1k, a.rstd1k, x.g_C, 1, x.gC_defined ? 1 : 0, Mk, 0, 0, 0);
-                x.gC_defined = true;
-            }
-        } else if (mode == MEBT_MODE_LATENT_DEC) {
-            ln1(a.q_in, sc.dqn, nullptr, a.mean1q, a.rstd1q, x.g_T, 0, 0, Mq, 0, 0, 0);
-            ln1(a.k_in, sc.dkn, nullptr, a.mean1k, a.rstd1k, x.g_S, 0, x.gS_defined ? 1 : 0, Mk, 0, 0, 0);
-            x.gS_defined = true;
-        } else {   // lt2l: key rows [0,NS) come from the same LN as the query
-            ln1(a.q_in, sc.dkn, sc.dqn, a.mean1k, a.rstd1k, x.g_S, 0, 0, B * NS, NS, NS + NT, 0);
-            ln1(a.k_in, sc.dkn, nullptr, a.mean1k, a.rstd1k, x.g_T, 0, x.gT_defined ? 1 : 0, B * NT, NT, NS + NT, NS);
-            x.gT_defined = true;
-        }
+    }
+    if (side) RC(fork_side(m, st));
+    RC(flush_or_park(m, lv, sd, side));
+    // LN1 backward, one job per stream the block read, in one launch (they share LN1's dgamma / dbeta): a query stream's gradient is
+    // overwritten (this block replaced the stream), a stream only the key read keeps what the blocks above left in it
+    LnBwdParams lj[MEBT_LN_MAXJ];
+    RouteSeg jb[RT_MAXJ];
+    const int nj = route_bwd_jobs(r, x.len, jb);
+    for (int j = 0; j < nj; ++j) {
+        const RouteSeg& g = jb[j];
+        const int s = g.stream;
+        lj[j] = ln_bwd_params(m, a.in[s], g.key ? sc.dkn : sc.dqn, g.add_q ? sc.dqn : nullptr, nullptr, o.ln1w, o.ln1b, g.key ? a.mean1k : a.mean1q,
+                              g.key ? a.rstd1k : a.rstd1q, x.g[s], g_f32(m, s), g.key_only && x.def[s], B * g.len, g.seg, g.stride, g.off);
+        if (g.len > 0) x.def[s] = true;
     }
     // The job that finalises the stream gradient the block below consumes also writes that block's dropout-masked copy
     // (its MLP branch gradient, dout * mask): one elementwise launch less per block.  Not with the side stream: the
     // leaves of block i+1 may still be reading the other scratch set's dout_m.
     static const int fuse_doutm = [] { const char* e = getenv("MEBT_FUSE_DOUTM"); return e ? atoi(e) : 1; }();
-    if (i > 0 && !side && p_res > 0.f && fuse_doutm && m->d.modes[i - 1] != MEBT_MODE_MASKGIT) {
-        const bool below_dec = m->d.modes[i - 1] == MEBT_MODE_LATENT_DEC;
-        const void* want = below_dec ? x.g_T : x.g_S;
+    if (i > 0 && !side && p_res > 0.f && fuse_doutm && route_of(m->d.modes[i - 1]).nq() == 1) {
+        const void* want = x.g[route_of(m->d.modes[i - 1]).q[0]];      // the gradient of the output of the block below
         int k = -1;
         for (int j = 0; j < nj; ++j) if (lj[j].dx == want) k = j;       // the last job writing it
         if (k >= 0 && !lj[k].dx_f32) {
@@ -1219,28 +1160,24 @@ extern "C" int mebt_gpt_backward(mebt_model* m, void* ws, const float* dlogits, 
     FwdCtx& x = m->ctx;
     hipStream_t st = S(stream);
     RC(input_grad_dropout(m, st));
-    const int d = m->d.n_embd, f32 = m->d.dtype == MEBT_F32;
-    struct { float* dst; const void* src; bool defined; long rows; int src_f32; } o[3] = {
-        {d_sos, x.g_S, x.gS_defined, (long)x.B * m->d.n_latent, f32}, {d_contexts, x.g_C, x.gC_defined, (long)x.B * x.NC, 1},
-        {d_targets, x.g_T, x.gT_defined, (long)x.B * x.NT, f32}};
-    for (auto& t : o) {
-        if (!t.dst || t.rows <= 0) continue;
-        if (t.defined) RC(launch_copy_rows(t.src, t.dst, t.rows, d, t.src_f32, 1, 0, 0, 0, 0, 0, 0, st));
-        else MEBT_HIP_CHECK(hipMemsetAsync(t.dst, 0, (size_t)t.rows * d * 4, st));      // the logits do not depend on this input
+    const int d = m->d.n_embd;
+    float* const dst[RT_STREAMS] = {d_sos, d_contexts, d_targets};
+    for (int s = 0; s < RT_STREAMS; ++s) {
+        const long rows = (long)x.B * x.len[s];
+        if (!dst[s] || rows <= 0) continue;
+        if (x.def[s]) RC(launch_copy_rows(x.g[s], dst[s], rows, d, g_f32(m, s), 1, 0, 0, 0, 0, 0, 0, st));
+        else MEBT_HIP_CHECK(hipMemsetAsync(dst[s], 0, (size_t)rows * d * 4, st));      // the logits do not depend on this input
     }
     return MEBT_OK;
 }
 
 static int input_grad_dropout(mebt_model* m, hipStream_t st) {
     FwdCtx& x = m->ctx;
-    if (x.drop_on && m->d.embd_pdrop > 0.f) {
-        const int f32 = m->d.dtype == MEBT_F32;
-        const size_t dd = m->d.n_embd;
-        const float pe = m->d.embd_pdrop;
-        if (x.gS_defined) RC(launch_apply_dropout(x.g_S, x.g_S, (size_t)x.B * m->d.n_latent * dd, f32, f32, make_drop(x.drop_seed, SITE_EMB_SOS, pe), st));
-        if (x.gT_defined) RC(launch_apply_dropout(x.g_T, x.g_T, (size_t)x.B * x.NT * dd, f32, f32, make_drop(x.drop_seed, SITE_EMB_TGT, pe), st));
-        if (x.gC_defined) RC(launch_apply_dropout(x.g_C, x.g_C, (size_t)x.B * x.NC * dd, 1, 1, make_drop(x.drop_seed, SITE_EMB_CTX, pe), st));
-    }
+    if (x.drop_on && m->d.embd_pdrop > 0.f)
+        for (int s : GRAD_ORDER)
+            if (x.def[s])
+                RC(launch_apply_dropout(x.g[s], x.g[s], (size_t)x.B * x.len[s] * m->d.n_embd, g_f32(m, s), g_f32(m, s),
+                                        make_drop(x.drop_seed, EMB_SITE[s], m->d.embd_pdrop), st));
     return MEBT_OK;
 }
 
@@ -1251,9 +1188,9 @@ extern "C" int mebt_backward_embed(mebt_model* m, void* ws, mebt_stream_t stream
     RC(input_grad_dropout(m, S(stream)));
     EmbedBwdParams p;
     p.x_ids = x.x_ids; p.ci = x.ci; p.ti = x.ti;
-    p.g_ctx = x.g_C; p.g_tgt = x.g_T; p.g_sos = x.g_S;
+    p.g_ctx = (const float*)x.g[RT_C]; p.g_tgt = x.g[RT_T]; p.g_sos = x.g[RT_S];
     p.g_tok_emb = m->gP + m->tok_emb; p.g_pos_emb = m->gP + m->pos_emb; p.g_mask_emb = m->gP + m->mask_emb; p.g_sos_emb = m->gP + m->sos_emb;
-    p.B = x.B; p.N = x.N; p.NC = x.gC_defined ? x.NC : 0; p.NT = x.gT_defined ? x.NT : 0; p.NS = x.gS_defined ? m->d.n_latent : 0; p.d = m->d.n_embd;
+    p.B = x.B; p.N = x.N; p.NC = x.def[RT_C] ? x.NC : 0; p.NT = x.def[RT_T] ? x.NT : 0; p.NS = x.def[RT_S] ? m->d.n_latent : 0; p.d = m->d.n_embd;
     if (p.NC != x.NC && x.NC > 0) {   // contexts unused by any live block: only the target rows scatter; keep index strides right
         mebt_set_error("backward_embed: contexts without a live latent_enc block are not supported");
         return MEBT_EINVAL;

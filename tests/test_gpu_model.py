@@ -230,3 +230,59 @@ def test_all_maskgit_without_latents(dtype):
             assert (gv[k].cpu() - ref).abs().max().item() / scale < lim, (t, k)
     with pytest.raises(_lib.MebtError, match="maskgit"):
         NativeModel(2, 2, 64, 16384, 0, 32, ["latent_enc", "maskgit"], dtype=dtype)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_blocks_the_loss_does_not_reach(dtype):
+    """The head reads the targets stream only, and only a latent_dec block writes it: the blocks above the last latent_dec one
+    (here a lt2l, a latent_self and a latent_enc block, one of each kind that can be dead) run in forward, get no gradient
+    and are skipped by AdamW the way torch skips `grad is None`.  Logits and every gradient vs the oracle autograd."""
+    modes = ["latent_enc", "latent_self", "latent_dec", "lt2l", "latent_self", "latent_enc"]
+    cfg = orc.OracleConfig(6, 2, 64, 32, 8, modes, shape=[2, 4, 4], budget=32, avg_loss=1.0)
+    P0 = orc.closed_form_params(cfg)
+    nm = build_native(cfg, dtype, P0)
+    shapes = orc.param_shapes(cfg)
+    dead = [k for k in shapes if k.split(".")[2:3] in (["3"], ["4"], ["5"]) and k.startswith("transformer.blocks.")]
+    assert len(dead) == 3 * 16
+    B = 2
+    x, idx = mg.inputs("micro", B, "dead-blocks")
+    for t in (0.5, 0.0):                         # t = 0 -> NC = 0
+        P = {k: v.clone().requires_grad_(True) for k, v in P0.items()}
+        logits, z_t, ntw, seq_len = orc.forward(P, cfg, x, idx, t, training=True)
+        _, _, loss = orc.loss_and_acc(logits, z_t, ntw, seq_len, cfg)
+        loss.backward()
+        assert all(P[k].grad is None for k in dead)
+        ci, ti, _ = orc.divide_indices(idx, t, cfg, True)
+        lg = nm.forward(x.reshape(B, -1).to(DEV), ci.to(DEV), ti.to(DEV), training=True)
+        # the logits pass through three live blocks of d = 64, as in test_all_maskgit_without_latents: 2 x BF16_TOL
+        tol = FP32_TIGHT if dtype == "f32" else 2 * BF16_TOL
+        err = (lg.cpu() - logits.detach()).abs().max().item()
+        print(f"[dead blocks {dtype} t {t}] max |dlogits| {err:.3e}")
+        assert err < tol, t
+        nm.backward(lg, 1.0 / (B * seq_len * (ntw / seq_len)))
+        torch.cuda.synchronize()
+        gv = nm.views(shapes, grads=True)
+        lim = 2e-3 if dtype == "f32" else BF16_GRAD_TOL
+        bad, worst = [], 0.0
+        for k, p in P.items():
+            ref = p.grad if p.grad is not None else torch.zeros_like(p)
+            # attn.key.bias has an exactly-zero gradient (softmax shift invariance): on the scale of its query sibling
+            sib = P[k.replace("attn.key.bias", "attn.query.bias")].grad
+            denom = (sib if sib is not None else ref).abs().max().item() + 1e-6
+            e = (gv[k].cpu() - ref).abs().max().item() / denom
+            worst = max(worst, e)
+            if not e < lim:
+                bad.append((k, round(e, 5), denom))
+        print(f"[dead blocks {dtype} t {t}] worst gradient error rel-to-max {worst:.3e}")
+        assert not bad, (t, bad[:20])
+        for k in dead:
+            assert not gv[k].any(), (t, k)
+    before = {k: v.clone() for k, v in nm.views(shapes).items()}
+    nm.adamw_step(1e-3, 0.1, 1)
+    torch.cuda.synchronize()
+    after = nm.views(shapes)
+    for k in dead:
+        assert torch.equal(after[k], before[k]), k
+    # block 0 is live: its six Linear weights decay whatever their gradient (at NC = 0 its attention biases get an exactly-zero one)
+    still = [k for k, shp in shapes.items() if k.startswith("transformer.blocks.0.") and len(shp) == 2 and torch.equal(after[k], before[k])]
+    assert not still, still
