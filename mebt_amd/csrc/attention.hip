@@ -281,29 +281,34 @@ static bool allow_lds(K kernel, int bytes) {
     return bytes <= 64 * 1024 || hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
 }
 
+// the split kernel unless MEBT_ATTN_GENERIC_SPLIT=1 (A/B: one wave per workgroup) or the streamed side is shorter than NS tiles
+template <int NS>
+static bool use_split(int streamed_rows) {
+    static const bool one = [] { const char* e = getenv("MEBT_ATTN_GENERIC_SPLIT"); return e && e[0] == '1'; }();
+    return NS > 1 && !one && streamed_rows >= NS * KT;
+}
+
 template <typename T, int HD>
 int run_fwd(const AttnParams& p, hipStream_t stream) {
     const dim3 grid((p.NQ + 63) / 64, p.H, p.B);
     constexpr int NS = split_of<HD>();
     static const bool ok_lds = allow_lds(&attn_fwd_generic<T, HD, NS>, attn_lds_bytes<HD, NS>());
     if (!ok_lds) { mebt_set_error("attention: cannot reserve the LDS of the split generic kernel"); return MEBT_EHIP; }
-    static const bool one = [] { const char* e = getenv("MEBT_ATTN_GENERIC_SPLIT"); return e && e[0] == '1'; }();     // A/B: 1 = one wave per workgroup
-    if (NS > 1 && !one && p.NK >= NS * KT) hipLaunchKernelGGL((attn_fwd_generic<T, HD, NS>), grid, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
+    if (use_split<NS>(p.NK)) hipLaunchKernelGGL((attn_fwd_generic<T, HD, NS>), grid, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
     else hipLaunchKernelGGL((attn_fwd_generic<T, HD, 1>), grid, dim3(64), (attn_lds_bytes<HD, 1>()), stream, p);
     return MEBT_OK;
 }
 template <typename T, int HD>
 int run_bwd(const AttnParams& p, hipStream_t stream) {
     constexpr int NS = split_of<HD>();
-    static const bool one = [] { const char* e = getenv("MEBT_ATTN_GENERIC_SPLIT"); return e && e[0] == '1'; }();
     static const bool ok_lds = allow_lds(&attn_bwd_dq_generic<T, HD, NS>, attn_lds_bytes<HD, NS>()) && allow_lds(&attn_bwd_dkv_generic<T, HD, NS>, attn_lds_bytes<HD, NS>());
     if (!ok_lds) { mebt_set_error("attention: cannot reserve the LDS of the split generic kernels"); return MEBT_EHIP; }
     const dim3 gq((p.NQ + 63) / 64, p.H, p.B);
-    if (NS > 1 && !one && p.NK >= NS * KT) hipLaunchKernelGGL((attn_bwd_dq_generic<T, HD, NS>), gq, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
+    if (use_split<NS>(p.NK)) hipLaunchKernelGGL((attn_bwd_dq_generic<T, HD, NS>), gq, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
     else hipLaunchKernelGGL((attn_bwd_dq_generic<T, HD, 1>), gq, dim3(64), (attn_lds_bytes<HD, 1>()), stream, p);
     if (p.NK > 0) {
         const dim3 gk((p.NK + 63) / 64, p.H, p.B);
-        if (NS > 1 && !one && p.NQ >= NS * KT) hipLaunchKernelGGL((attn_bwd_dkv_generic<T, HD, NS>), gk, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
+        if (use_split<NS>(p.NQ)) hipLaunchKernelGGL((attn_bwd_dkv_generic<T, HD, NS>), gk, dim3(64 * NS), (attn_lds_bytes<HD, NS>()), stream, p);
         else hipLaunchKernelGGL((attn_bwd_dkv_generic<T, HD, 1>), gk, dim3(64), (attn_lds_bytes<HD, 1>()), stream, p);
     }
     return MEBT_OK;
@@ -314,20 +319,14 @@ int run_bwd(const AttnParams& p, hipStream_t stream) {
 #ifdef MEBT_HAVE_ATTN_MFMA
 int launch_attn_fwd_mfma(const AttnParams& p, hipStream_t stream);   // attention_mfma.hip
 int launch_attn_bwd_mfma(const AttnParams& p, hipStream_t stream);
+static int g_force_generic = 0;
+void mebt_attn_force_generic(int on) { g_force_generic = on; }
 #else
 static int launch_attn_fwd_mfma(const AttnParams&, hipStream_t) { return -1; }
 static int launch_attn_bwd_mfma(const AttnParams&, hipStream_t) { return -1; }
 int launch_attn_block_order_probe(int, int, int, int, int32_t*, hipStream_t) { mebt_set_error("built without the MFMA attention"); return MEBT_EINVAL; }
 extern "C" int32_t mebt_debug_attn_last_launch(int32_t out[4]) { if (out) out[0] = out[1] = out[2] = out[3] = 0; return 0; }
-#endif
-#ifdef MEBT_HAVE_ATTN_MFMA
-static int g_force_generic = 0;
-#else
 static int g_force_generic = 1;
-#endif
-#ifdef MEBT_HAVE_ATTN_MFMA
-void mebt_attn_force_generic(int on) { g_force_generic = on; }
-#else
 void mebt_attn_force_generic(int) {}
 #endif
 

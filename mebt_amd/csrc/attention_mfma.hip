@@ -16,6 +16,9 @@
 // trip.  The operand that must be read column-wise (V in forward, K in dQ, Q/dO in dK/dV) comes
 // from the same row-major LDS image through ds_read_b64_tr_b16.
 //
+// Shared pieces: FragOffsets (fragment addresses), ChunkDma (chunk copies), FwdBlock and the steps of a forward pass (both forward
+// kernels), BwdBase / KeepBits (both backward roles), kFwdForms (the forward forms the launcher chooses among).
+//
 // LDS tile image: [64 rows][64 bf16] = 128-byte rows, 16-byte chunk index XOR-swizzled with
 // ((row >> 1) & 3) << 1, which is conflict-free for both the ds_read_b128 row reads and the
 // transposed reads used here.
@@ -35,28 +38,10 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 3) << 1; }
 
-// row-wise fragment: 16 rows (blk16) x 32 k (ks): lane l holds row l&15, k = 32ks + 8(l>>4) + j
-__device__ __forceinline__ bf16x8 frag_rows(const char* tile, int blk16, int ks, int lane) {
-    const int row = blk16 * 16 + (lane & 15);
-    const int c = 4 * ks + (lane >> 4);
-    return *reinterpret_cast<const bf16x8*>(tile + row * 128 + ((c ^ swz(row)) << 4));
-}
-// column-wise fragment (transposed read): the operand's "row" is tile column 16*cb + (l&15); its
-// k index 8g + j maps to tile row  32*kk + 16*(j>>2) + 4g + (j&3)  — the order in which a pair of
-// 16-row score accumulators presents its rows (see pack_acc).
-__device__ __forceinline__ bf16x8 frag_cols(const char* tile, int cb, int kk, int lane) {
-    const int g = lane >> 4, i = lane & 15, q4 = i >> 2, pp = i & 3;
-    const int ch = 2 * cb + (pp >> 1);
-    const int r0 = 32 * kk + 4 * g + q4, r1 = r0 + 16;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + r0 * 128 + ((ch ^ swz(r0)) << 4) + 8 * (pp & 1)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + r1 * 128 + ((ch ^ swz(r1)) << 4) + 8 * (pp & 1)));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
 // The fragment byte offsets depend only on the lane: computed once per kernel, the loop adds the stage base.
 struct FragOffsets {
-    int rows[4][2];        // frag_rows(blk16, ks)
-    int cols[4][2][2];     // frag_cols(cb, kk): the two transposed reads
+    int rows[4][2];        // row_frag(b, ks)
+    int cols[4][2][2];     // col_frag(cb, kk): the two transposed reads
     __device__ __forceinline__ void init(int lane) {
         const int g = lane >> 4, i = lane & 15, q4 = i >> 2, pp = i & 3;
 #pragma unroll
@@ -76,9 +61,13 @@ struct FragOffsets {
                 cols[cb][kk][1] = r1 * 128 + ((ch ^ swz(r1)) << 4) + 8 * (pp & 1);
             }
     }
+    // row-wise fragment: 16 rows (block b) x 32 k (ks): lane l holds row l&15, k = 32ks + 8(l>>4) + j
     __device__ __forceinline__ bf16x8 row_frag(const char* tile, int b, int ks) const {
         return *reinterpret_cast<const bf16x8*>(tile + rows[b][ks]);
     }
+    // column-wise fragment (transposed read): the operand's "row" is tile column 16*cb + (l&15); its
+    // k index 8g + j maps to tile row  32*kk + 16*(j>>2) + 4g + (j&3)  — the order in which a pair of
+    // 16-row score accumulators presents its rows (see pack_acc).
     __device__ __forceinline__ bf16x8 col_frag(const char* tile, int cb, int kk) const {
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + cols[cb][kk][0]));
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile + cols[cb][kk][1]));
@@ -105,18 +94,15 @@ __device__ __forceinline__ bf16x8 frag_global(const bf16_t* base, int row, int r
 // xor-32 butterfly step.  __shfl_xor compiled to ds_bpermute_b32 + s_waitcnt lgkmcnt(0): four exposed LDS round trips per 64-key tile
 // in the forward's softmax (profiles/r04_attention_forward.txt).
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float group_sum(float v) {   // across the 4 lane groups (same l&15)
+template <typename Op>
+__device__ __forceinline__ float group_reduce(float v, Op op) {   // across the 4 lane groups (same l&15)
     u32x2_t r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    v = op(__uint_as_float(r[0]), __uint_as_float(r[1]));
     r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    return op(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-__device__ __forceinline__ float group_max(float v) {
-    u32x2_t r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
+__device__ __forceinline__ float group_sum(float v) { return group_reduce(v, [](float a, float b) { return a + b; }); }
+__device__ __forceinline__ float group_max(float v) { return group_reduce(v, [](float a, float b) { return fmaxf(a, b); }); }
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
 
 // Block order.  Every launch is a 1-D grid of T = X row blocks x H heads x B samples; the dispatcher deals consecutive workgroup
@@ -218,6 +204,156 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // groups' (m, l, O) are merged through LDS at the end — twice the waves per query row without a second kernel or partial results
 // in HBM.  The groups run in lock step (the workgroup barrier is shared): a group without a chunk in an iteration only keeps the
 // barrier count.
+//
+// attn_fwd_mfma and attn_fwd_pp differ in their schedule only.  What a workgroup sets up (FwdBlock) and the arithmetic of a pass over
+// two 64-key tiles (mask_beyond .. store_out below) exist once; the kernels own the loops, the waits and the order of issue.
+
+// The prologue of a forward block: its (b, h), this lane's query row and its two Q fragments, the K and V chunk copies, and the index
+// list of a gathered key set staged behind the rings.  The order of issue is part of the contract (the counted waits of the kernels
+// see DMAs only): Q fragments, then the index list (plain loads, waited for here), then whatever the kernel issues.
+template <int NW>
+struct FwdBlock {
+    int b, h, q;
+    bool gather;            // keys / values = rows kidx[b, :] of a cache of kidx_rows positions per sample
+    bf16x8 qf[2];
+    ChunkDma<NW> lk, lv;
+    int* sidx;
+    __device__ __forceinline__ void init(const AttnParams& p, int tid, int wave, int nthreads, char* behind_rings) {
+        const int lane = tid & 63;
+        const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + NW * 16 - 1) / (NW * 16), p.H, p.xcd_order);
+        b = bp.b, h = bp.h;
+        q = bp.x * (NW * 16) + wave * 16 + (lane & 15);
+        const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
+        gather = p.kidx != nullptr;
+        const int krows = gather ? p.kidx_rows : p.NK;
+        const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * krows * p.ldk + h * 64;
+        const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * krows * p.ldv + h * 64;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) qf[ks] = frag_global(Q, q, p.NQ, p.ldq, ks, lane);
+        lk.init(K, krows, p.ldk, wave, lane);
+        lv.init(V, krows, p.ldv, wave, lane);
+        // gathered keys: this sample's index list goes to LDS behind the rings first (plain loads, older than every DMA of the kernel
+        // and waited for here: the counted waits of the loop see DMAs only)
+        sidx = reinterpret_cast<int*>(behind_rings);
+        if (gather) {
+            const int32_t* gi = p.kidx + (size_t)b * p.NK;
+            for (int i = tid; i < p.NK; i += nthreads) sidx[i] = gi[i];
+            __syncthreads();
+        }
+    }
+    // chunk `chunk` of K / of V into the image at dst: contiguous rows, or the rows the index list names
+    __device__ __forceinline__ void issue_k(const AttnParams& p, char* dst, int chunk, int wave, int lane) const {
+        if (gather) lk.issue_gather(dst, chunk, wave, lane, sidx, p.NK, p.ldk);
+        else lk.issue(dst, chunk, wave);
+    }
+    __device__ __forceinline__ void issue_v(const AttnParams& p, char* dst, int chunk, int wave, int lane) const {
+        if (gather) lv.issue_gather(dst, chunk, wave, lane, sidx, p.NK, p.ldv);
+        else lv.issue(dst, chunk, wave);
+    }
+};
+
+// The steps of a pass.  s[u][kb][r] = S^T[key][q] of key k0 + 64 u + 16 kb + 4 g + r: the two 64-key tiles that start at key k0.
+// ragged end only: keys beyond NK are masked out
+__device__ __forceinline__ void mask_beyond(f32x4 (&s)[2][4], int k0, int NK, int g) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            f32x4 v = s[u][kb];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (k0 + 64 * u + 16 * kb + 4 * g + r >= NK) v[r] = -INFINITY;
+            s[u][kb] = v;
+        }
+}
+// the row maximum of the scaled scores
+__device__ __forceinline__ float scores_max(const f32x4 (&s)[2][4], float c) {
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, s[u][kb][r]);
+    return group_max(tmax) * c;                       // c > 0: max commutes with the scale
+}
+// scores -> probabilities against the new running maximum; (m, l, o) follow
+__device__ __forceinline__ void softmax_step(f32x4 (&s)[2][4], float tmax, float c, float& m, float& l, f32x4 (&o)[4]) {
+    const float mn = fmaxf(m, tmax);
+    float ps = 0.f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { s[u][kb][r] = fast_exp2(fmaf(s[u][kb][r], c, -mn)); ps += s[u][kb][r]; }
+    ps = group_sum(ps);
+    // the running maximum moves in the first tiles and then rarely: when no lane of the wave saw it move, alpha = exp2(0) = 1
+    // exactly and the rescale of l and of the 16 output accumulators is skipped (same values, 17 vector instructions less)
+    if (__builtin_amdgcn_ballot_w64(mn != m)) {
+        const float alpha = fast_exp2(m - mn);
+        l *= alpha;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] *= alpha;
+    }
+    l += ps;
+    m = mn;
+}
+// attn_drop on the probabilities (gpt.py:135); the row sum of softmax_step stays undropped.  A tile that starts at or beyond NK is
+// skipped.  row = (b H + h) NQ + q; dmask (if any, and for a valid query row) takes the keep bits of this lane's 16 elements of a
+// tile, read back by the backward kernels.  The score array is only ever updated four values at a time here and in mask_beyond, and
+// the params struct stays out of this signature: with p passed whole attn_fwd_pp (256 VGPRs) spilled 3 VGPRs to 16 B of scratch.
+__device__ __forceinline__ void drop_scores(f32x4 (&s)[2][4], const DropCfg& drop, uint16_t* dmask, bool qvalid, uint64_t row, int NK, int g, int k0, int mtiles) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (k0 + 64 * u >= NK) break;
+        const uint64_t dbase = row * NK + k0 + 64 * u;
+        uint32_t bits = 0;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const f32x4 keep = drop_keep4(drop, dbase + 16 * kb + 4 * g);
+            s[u][kb] *= keep;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bits |= (keep[r] != 0.f ? 1u : 0u) << (4 * kb + r);
+        }
+        if (dmask && qvalid) dmask[((size_t)row * mtiles + ((k0 >> 6) + u)) * 4 + g] = (uint16_t)bits;
+    }
+}
+// Two groups of waves on the same query rows: group 1 parks (m, l, O) in LDS, group 0 combines.  False for group 1, which is done.
+__device__ __forceinline__ bool merge_groups(char* smem_all, int half, int wave, int lane, float& m, float& l, f32x4 (&o)[4]) {
+    __syncthreads();                         // both rings are idle
+    float* mg = reinterpret_cast<float*>(smem_all) + (size_t)(wave * 64 + lane) * 18;
+    if (half == 1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mg[4 * e + r] = o[e][r];
+        mg[16] = m; mg[17] = l;
+    }
+    __syncthreads();
+    if (half == 1) return false;
+    const float m1 = mg[16], l1 = mg[17];
+    const float mn = fmaxf(m, m1);
+    const float a0 = m == mn ? 1.f : fast_exp2(m - mn), a1 = m1 == mn ? 1.f : fast_exp2(m1 - mn);    // -inf == -inf cannot occur: NK > 0
+    l = l * a0 + l1 * a1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[e][r] = o[e][r] * a0 + mg[4 * e + r] * a1;
+    m = mn;
+    return true;
+}
+// o / l and lse = m ln 2 + ln l of this lane's query row
+__device__ __forceinline__ void store_out(const AttnParams& p, int b, int h, int q, int g, float m, float l, const f32x4 (&o)[4]) {
+    if (q < p.NQ) {
+        const float inv = 1.0f / l;
+        bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + ((size_t)b * p.NQ + q) * p.ldo + h * 64;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) store4<bf16_t>(O + 16 * e + 4 * g, o[e] * inv);
+        if (p.lse && g == 0) p.lse[((size_t)b * p.H + h) * p.NQ + q] = m * 0.6931471805599453f + logf(l);
+    }
+}
+
 template <int NW, int NST, int SPLIT = 1>
 __global__ __launch_bounds__(NW * SPLIT * 64) void attn_fwd_mfma(const AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem_all[];
@@ -226,41 +362,17 @@ __global__ __launch_bounds__(NW * SPLIT * 64) void attn_fwd_mfma(const AttnParam
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = SPLIT == 1 ? 0 : wave_all / NW, wave = SPLIT == 1 ? wave_all : wave_all % NW;
     char* smem = smem_all + half * (NST * SBYTES);
-    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + NW * 16 - 1) / (NW * 16), p.H, p.xcd_order);
-    const int b = bp.b, h = bp.h;
-    const int q = bp.x * (NW * 16) + wave * 16 + (lane & 15);
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
-    const bool gather = p.kidx != nullptr;          // keys / values = rows kidx[b, :] of a cache of kidx_rows positions per sample
-    const int krows = gather ? p.kidx_rows : p.NK;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * krows * p.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * krows * p.ldv + h * 64;
-    bf16x8 qf[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) qf[ks] = frag_global(Q, q, p.NQ, p.ldq, ks, lane);
-    ChunkDma<NW> lk, lv;
-    lk.init(K, krows, p.ldk, wave, lane);
-    lv.init(V, krows, p.ldv, wave, lane);
-    // gathered keys: this sample's index list goes to LDS behind the rings first (plain loads, older than every DMA of the kernel
-    // and waited for here: the counted waits of the loop see DMAs only)
-    int* sidx = reinterpret_cast<int*>(smem_all + SPLIT * NST * SBYTES);
-    if (gather) {
-        const int32_t* gi = p.kidx + (size_t)b * p.NK;
-        for (int i = tid; i < p.NK; i += NW * SPLIT * 64) sidx[i] = gi[i];
-        __syncthreads();
-    }
+    FwdBlock<NW> fb;
+    fb.init(p, tid, wave, NW * SPLIT * 64, smem_all + SPLIT * NST * SBYTES);
+    const int b = fb.b, h = fb.h, q = fb.q;
     const int nchunks_all = (p.NK + CROWS - 1) / CROWS;
     const int nchunks = SPLIT == 1 ? nchunks_all : (nchunks_all - half + SPLIT - 1) / SPLIT;      // this group's chunks: half, half + SPLIT, ...
     const int niter = (nchunks_all + SPLIT - 1) / SPLIT;                                            // barrier rounds of the workgroup
 #pragma unroll
     for (int a = 0; a < NST; ++a)
         if (a < nchunks) {
-            if (gather) {
-                lk.issue_gather(smem + a * SBYTES, a * SPLIT + half, wave, lane, sidx, p.NK, p.ldk);
-                lv.issue_gather(smem + a * SBYTES + CBYTES, a * SPLIT + half, wave, lane, sidx, p.NK, p.ldv);
-            } else {
-                lk.issue(smem + a * SBYTES, a * SPLIT + half, wave);
-                lv.issue(smem + a * SBYTES + CBYTES, a * SPLIT + half, wave);
-            }
+            fb.issue_k(p, smem + a * SBYTES, a * SPLIT + half, wave, lane);
+            fb.issue_v(p, smem + a * SBYTES + CBYTES, a * SPLIT + half, wave, lane);
         }
     const float c = 0.125f * LOG2E;     // 1/sqrt(64) folded with log2(e)
     const int mtiles = mebt_attn_dmask_tiles(p.NK);
@@ -300,62 +412,12 @@ __global__ __launch_bounds__(NW * SPLIT * 64) void attn_fwd_mfma(const AttnParam
                 for (int kb = 0; kb < 4; ++kb) {
                     s[u][kb] = f32x4{0, 0, 0, 0};
 #pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) s[u][kb] = MFMA(fo.row_frag(sK + u * TILE_BYTES, kb, ks), qf[ks], s[u][kb]);
+                    for (int ks = 0; ks < 2; ++ks) s[u][kb] = MFMA(fo.row_frag(sK + u * TILE_BYTES, kb, ks), fb.qf[ks], s[u][kb]);
                 }
             const int k0 = ch * CROWS + t * TILE;
-            float tmax = -INFINITY;
-            if (k0 + 2 * TILE > p.NK) {     // ragged end only: keys beyond NK are masked out
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (k0 + 64 * u + 16 * kb + 4 * g + r >= p.NK) s[u][kb][r] = -INFINITY;
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, s[u][kb][r]);
-            tmax = group_max(tmax) * c;                       // c > 0: max commutes with the scale
-            const float mn = fmaxf(m, tmax);
-            float ps = 0.f;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { s[u][kb][r] = fast_exp2(fmaf(s[u][kb][r], c, -mn)); ps += s[u][kb][r]; }
-            ps = group_sum(ps);
-            // the running maximum moves in the first tiles and then rarely: when no lane of the wave saw it move, alpha = exp2(0) = 1
-            // exactly and the rescale of l and of the 16 output accumulators is skipped (same values, 17 vector instructions less)
-            if (__builtin_amdgcn_ballot_w64(mn != m)) {
-                const float alpha = fast_exp2(m - mn);
-                l *= alpha;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] *= alpha;
-            }
-            l += ps;
-            m = mn;
-            if (p.drop.thresh) {   // attn_drop on the probabilities (gpt.py:135); the row sum above stays undropped
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    if (t + u >= nt) break;
-                    const uint64_t dbase = (((uint64_t)b * p.H + h) * p.NQ + q) * p.NK + k0 + 64 * u;
-                    uint32_t bits = 0;
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) {
-                        const f32x4 keep = drop_keep4(p.drop, dbase + 16 * kb + 4 * g);
-                        s[u][kb] *= keep;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) bits |= (keep[r] != 0.f ? 1u : 0u) << (4 * kb + r);
-                    }
-                    if (p.dmask && q < p.NQ)      // the keep bits of this lane's 16 elements: read back by the backward kernels
-                        p.dmask[((((size_t)b * p.H + h) * p.NQ + q) * mtiles + ((k0 >> 6) + u)) * 4 + g] = (uint16_t)bits;
-                }
-            }
+            if (k0 + 2 * TILE > p.NK) mask_beyond(s, k0, p.NK, g);
+            softmax_step(s, scores_max(s, c), c, m, l, o);
+            if (p.drop.thresh) drop_scores(s, p.drop, p.dmask, q < p.NQ, ((uint64_t)b * p.H + h) * p.NQ + q, p.NK, g, k0, mtiles);
             // O^T[e][q] += V^T[e][key] P^T[key][q]
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -369,46 +431,14 @@ __global__ __launch_bounds__(NW * SPLIT * 64) void attn_fwd_mfma(const AttnParam
         if (SPLIT == 1 ? ci + NST < nchunks : it + NST < niter) {      // SPLIT: both groups keep the same barrier count
             __builtin_amdgcn_s_barrier();                     // every wave is done reading this stage
             if (ci + NST < nchunks) {
-                if (gather) {
-                    lk.issue_gather(stage, (ci + NST) * SPLIT + half, wave, lane, sidx, p.NK, p.ldk);
-                    lv.issue_gather(stage + CBYTES, (ci + NST) * SPLIT + half, wave, lane, sidx, p.NK, p.ldv);
-                } else {
-                    lk.issue(stage, (ci + NST) * SPLIT + half, wave);
-                    lv.issue(stage + CBYTES, (ci + NST) * SPLIT + half, wave);
-                }
+                fb.issue_k(p, stage, (ci + NST) * SPLIT + half, wave, lane);
+                fb.issue_v(p, stage + CBYTES, (ci + NST) * SPLIT + half, wave, lane);
             }
         }
         if (++st == NST) st = 0;
     }
-    if (SPLIT > 1) {                             // merge the groups: group 1 parks (m, l, O) in LDS, group 0 combines
-        __syncthreads();                         // both rings are idle
-        float* mg = reinterpret_cast<float*>(smem_all) + (size_t)(wave * 64 + lane) * 18;
-        if (half == 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) mg[4 * e + r] = o[e][r];
-            mg[16] = m; mg[17] = l;
-        }
-        __syncthreads();
-        if (half == 1) return;
-        const float m1 = mg[16], l1 = mg[17];
-        const float mn = fmaxf(m, m1);
-        const float a0 = m == mn ? 1.f : fast_exp2(m - mn), a1 = m1 == mn ? 1.f : fast_exp2(m1 - mn);    // -inf == -inf cannot occur: NK > 0
-        l = l * a0 + l1 * a1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[e][r] = o[e][r] * a0 + mg[4 * e + r] * a1;
-        m = mn;
-    }
-    if (q < p.NQ) {
-        const float inv = 1.0f / l;
-        bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + ((size_t)b * p.NQ + q) * p.ldo + h * 64;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) store4<bf16_t>(O + 16 * e + 4 * g, o[e] * inv);
-        if (p.lse && g == 0) p.lse[((size_t)b * p.H + h) * p.NQ + q] = m * 0.6931471805599453f + logf(l);
-    }
+    if (SPLIT > 1 && !merge_groups(smem_all, half, wave, lane, m, l, o)) return;
+    store_out(p, b, h, q, g, m, l, o);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -430,38 +460,15 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wave_all >> 2, wave = wave_all & 3;
     char* smem = smem_all + half * (2 * SBYTES);
-    const BlockPos bp = attn_block_pos(blockIdx.x, gridDim.x, (p.NQ + NW * 16 - 1) / (NW * 16), p.H, p.xcd_order);
-    const int b = bp.b, h = bp.h;
-    const int q = bp.x * (NW * 16) + wave * 16 + (lane & 15);
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
-    const bool gather = p.kidx != nullptr;
-    const int krows = gather ? p.kidx_rows : p.NK;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * krows * p.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * krows * p.ldv + h * 64;
-    bf16x8 qf[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) qf[ks] = frag_global(Q, q, p.NQ, p.ldq, ks, lane);
-    ChunkDma<NW> lk, lv;
-    lk.init(K, krows, p.ldk, wave, lane);
-    lv.init(V, krows, p.ldv, wave, lane);
-    int* sidx = reinterpret_cast<int*>(smem_all + 4 * SBYTES);
-    if (gather) {
-        const int32_t* gi = p.kidx + (size_t)b * p.NK;
-        for (int i = tid; i < p.NK; i += 512) sidx[i] = gi[i];
-        __syncthreads();
-    }
+    FwdBlock<NW> fb;
+    fb.init(p, tid, wave, 512, smem_all + 4 * SBYTES);
+    const int b = fb.b, h = fb.h, q = fb.q;
     const int nchunks_all = (p.NK + CROWS - 1) / CROWS;
     const int n = (nchunks_all - half + 1) / 2;                     // this group's chunks: half, half + 2, ...
     const int n0 = (nchunks_all + 1) / 2, n1 = nchunks_all / 2;
     const int nphase = max(2 * n0 + 1, 2 * n1 + 2);                // group 0: phases 0 .. 2 n0, group 1: 1 .. 2 n1 + 1
-    auto issue_k = [&](int j) {
-        if (gather) lk.issue_gather(smem + (j & 1) * SBYTES, 2 * j + half, wave, lane, sidx, p.NK, p.ldk);
-        else lk.issue(smem + (j & 1) * SBYTES, 2 * j + half, wave);
-    };
-    auto issue_v = [&](int j) {
-        if (gather) lv.issue_gather(smem + (j & 1) * SBYTES + CBYTES, 2 * j + half, wave, lane, sidx, p.NK, p.ldv);
-        else lv.issue(smem + (j & 1) * SBYTES + CBYTES, 2 * j + half, wave);
-    };
+    auto issue_k = [&](int j) { fb.issue_k(p, smem + (j & 1) * SBYTES, 2 * j + half, wave, lane); };
+    auto issue_v = [&](int j) { fb.issue_v(p, smem + (j & 1) * SBYTES + CBYTES, 2 * j + half, wave, lane); };
     if (0 < n) { issue_k(0); issue_v(0); }
     if (1 < n) issue_k(1);
     if (n <= 0) wait_vm<0>();                   // K(0) has landed (this wave's pieces); V(0) and K(1) may stay in flight
@@ -517,29 +524,14 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) s[u][kb] = MFMA(kf[u][kb][0], qf[0], (f32x4{0, 0, 0, 0}));
+                    for (int kb = 0; kb < 4; ++kb) s[u][kb] = MFMA(kf[u][kb][0], fb.qf[0], (f32x4{0, 0, 0, 0}));
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) s[u][kb] = MFMA(kf[u][kb][1], qf[1], s[u][kb]);
+                    for (int kb = 0; kb < 4; ++kb) s[u][kb] = MFMA(kf[u][kb][1], fb.qf[1], s[u][kb]);
                 const int k0 = (2 * i + half) * CROWS;
-                if (k0 + CROWS > p.NK) {        // ragged end only: keys beyond NK are masked out
-#pragma unroll
-                    for (int u = 0; u < 2; ++u)
-#pragma unroll
-                        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                            for (int rr = 0; rr < 4; ++rr)
-                                if (k0 + 64 * u + 16 * kb + 4 * g + rr >= p.NK) s[u][kb][rr] = -INFINITY;
-                }
-                float t = -INFINITY;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) t = fmaxf(t, s[u][kb][rr]);
-                tmax = group_max(t) * c;
+                if (k0 + CROWS > p.NK) mask_beyond(s, k0, p.NK, g);
+                tmax = scores_max(s, c);
             }
         } else {
             // ---- vector phase: refill the halves the matrix phase has just released, softmax of S(i)
@@ -547,40 +539,8 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
             if (more_v) issue_v(i + 1);
             if (more_k) issue_k(i + 2);
             const int k0 = (2 * i + half) * CROWS;
-            const float mn = fmaxf(m, tmax);
-            float ps = 0.f;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) { s[u][kb][rr] = fast_exp2(fmaf(s[u][kb][rr], c, -mn)); ps += s[u][kb][rr]; }
-            ps = group_sum(ps);
-            if (__builtin_amdgcn_ballot_w64(mn != m)) {
-                const float alpha = fast_exp2(m - mn);
-                l *= alpha;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] *= alpha;
-            }
-            l += ps;
-            m = mn;
-            if (p.drop.thresh) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    if (k0 + 64 * u >= p.NK) break;
-                    const uint64_t dbase = (((uint64_t)b * p.H + h) * p.NQ + q) * p.NK + k0 + 64 * u;
-                    uint32_t bits = 0;
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) {
-                        const f32x4 keep = drop_keep4(p.drop, dbase + 16 * kb + 4 * g);
-                        s[u][kb] *= keep;
-#pragma unroll
-                        for (int rr = 0; rr < 4; ++rr) bits |= (keep[rr] != 0.f ? 1u : 0u) << (4 * kb + rr);
-                    }
-                    if (p.dmask && q < p.NQ)
-                        p.dmask[((((size_t)b * p.H + h) * p.NQ + q) * mtiles + ((k0 >> 6) + u)) * 4 + g] = (uint16_t)bits;
-                }
-            }
+            softmax_step(s, tmax, c, m, l, o);
+            if (p.drop.thresh) drop_scores(s, p.drop, p.dmask, q < p.NQ, ((uint64_t)b * p.H + h) * p.NQ + q, p.NK, g, k0, mtiles);
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -591,37 +551,36 @@ __global__ __launch_bounds__(512) void attn_fwd_pp(const AttnParams p) {
             else wait_vm<0>();
         }
     }
-    // merge the groups: group 1 parks (m, l, O) in LDS, group 0 combines
-    __syncthreads();
-    float* mg = reinterpret_cast<float*>(smem_all) + (size_t)(wave * 64 + lane) * 18;
-    if (half == 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) mg[4 * e + rr] = o[e][rr];
-        mg[16] = m; mg[17] = l;
-    }
-    __syncthreads();
-    if (half == 1) return;
-    {
-        const float m1 = mg[16], l1 = mg[17];
-        const float mn = fmaxf(m, m1);
-        const float a0 = m == mn ? 1.f : fast_exp2(m - mn), a1 = m1 == mn ? 1.f : fast_exp2(m1 - mn);
-        l = l * a0 + l1 * a1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) o[e][rr] = o[e][rr] * a0 + mg[4 * e + rr] * a1;
-        m = mn;
-    }
-    if (q < p.NQ) {
-        const float inv = 1.0f / l;
-        bf16_t* O = reinterpret_cast<bf16_t*>(p.o) + ((size_t)b * p.NQ + q) * p.ldo + h * 64;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) store4<bf16_t>(O + 16 * e + 4 * g, o[e] * inv);
-        if (p.lse && g == 0) p.lse[((size_t)b * p.H + h) * p.NQ + q] = m * 0.6931471805599453f + logf(l);
-    }
+    if (!merge_groups(smem_all, half, wave, lane, m, l, o)) return;
+    store_out(p, b, h, q, g, m, l, o);
 }
+
+// ------------------------------------------------------------------------------------------------
+// backward, both roles: the operand bases of a (b, h) and its keep bits
+// ------------------------------------------------------------------------------------------------
+struct BwdBase {
+    const bf16_t *Q, *G, *Oo, *K, *V;
+    __device__ __forceinline__ BwdBase(const AttnParams& p, int b, int h) {
+        Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
+        G = reinterpret_cast<const bf16_t*>(p.d_o) + (size_t)b * p.NQ * p.lddo + h * 64;
+        Oo = reinterpret_cast<const bf16_t*>(p.o) + (size_t)b * p.NQ * p.ldo + h * 64;
+        K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * p.NK * p.ldk + h * 64;
+        V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * p.NK * p.ldv + h * 64;
+    }
+};
+// The keep bits of a (b, h) as a buffer: NQ rows of mtiles x 8 bytes.  A null / zero-sized mask reads as zeros without traffic, so
+// both roles issue their mask pieces always and their counted waits stay the same.
+struct KeepBits {
+    bool use;               // dropout with a keep-bit buffer (else the hash, or no dropout)
+    int mtiles;
+    __amdgpu_buffer_rsrc_t rsrc;
+    __device__ __forceinline__ KeepBits(const AttnParams& p, int b, int h) {
+        use = p.drop.thresh && p.dmask != nullptr;
+        mtiles = mebt_attn_dmask_tiles(p.NK);
+        const size_t mrow0 = ((size_t)b * p.H + h) * p.NQ;
+        rsrc = make_rsrc(p.dmask ? p.dmask + mrow0 * mtiles * 4 : (const uint16_t*)p.q, use ? (size_t)p.NQ * mtiles * 8 : 0);
+    }
+};
 
 // ------------------------------------------------------------------------------------------------
 // backward: dQ (+ delta = rowsum(dO * O)).  One wave = 16 query rows; K/V chunks streamed.  Row block xb of (b, h).
@@ -631,11 +590,8 @@ __device__ __forceinline__ void bwd_dq_block(const AttnParams& p, char* smem, in
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = xb * BLOCK_ROWS + wave * 16 + (lane & 15);
     const bool qv = q < p.NQ;
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
-    const bf16_t* G = reinterpret_cast<const bf16_t*>(p.d_o) + (size_t)b * p.NQ * p.lddo + h * 64;
-    const bf16_t* Oo = reinterpret_cast<const bf16_t*>(p.o) + (size_t)b * p.NQ * p.ldo + h * 64;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * p.NK * p.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * p.NK * p.ldv + h * 64;
+    const BwdBase bb(p, b, h);
+    const bf16_t *Q = bb.Q, *G = bb.G, *Oo = bb.Oo, *K = bb.K, *V = bb.V;
     ChunkDma<> lk, lv;
     lk.init(K, p.NK, p.ldk, wave, lane);
     lv.init(V, p.NK, p.ldv, wave, lane);
@@ -654,13 +610,12 @@ __device__ __forceinline__ void bwd_dq_block(const AttnParams& p, char* smem, in
     // keep bits of (this workgroup's 128 queries) x (the chunk's 4 key tiles): 32 B per query = 4 KiB per chunk = four 1-KiB DMA
     // pieces, issued by waves 0-3 with the chunk (always: a null / zero-sized mask reads as zeros without traffic, and the
     // counted waits stay the same); piece `wave`, lane l -> query 32 wave + l / 2, 16-byte half l & 1
-    const bool use_bits = p.drop.thresh && p.dmask != nullptr;
-    const int mtiles = mebt_attn_dmask_tiles(p.NK);
-    const size_t mrow0 = ((size_t)b * p.H + h) * p.NQ;
-    const __amdgpu_buffer_rsrc_t rmask = make_rsrc(p.dmask ? p.dmask + mrow0 * mtiles * 4 : (const uint16_t*)p.q, use_bits ? (size_t)p.NQ * mtiles * 8 : 0);
+    const KeepBits km(p, b, h);
+    const bool use_bits = km.use;
+    const int mtiles = km.mtiles;
     const uint32_t moff = (uint32_t)((xb * BLOCK_ROWS + 32 * (wave & 3) + (lane >> 1)) * mtiles * 8 + (lane & 1) * 16);
     auto issue_mask = [&](char* stage, int chunk) {
-        if (wave < 4) dma16(rmask, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * 32);
+        if (wave < 4) dma16(km.rsrc, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * 32);
     };
     lk.issue(smem, 0, wave);
     lv.issue(smem + CHUNK_BYTES, 0, wave);
@@ -757,11 +712,8 @@ __device__ __forceinline__ void bwd_dkv_block(const AttnParams& p, char* smem, i
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int key = xb * BLOCK_ROWS + wave * 16 + (lane & 15);
-    const bf16_t* Q = reinterpret_cast<const bf16_t*>(p.q) + (size_t)b * p.NQ * p.ldq + h * 64;
-    const bf16_t* G = reinterpret_cast<const bf16_t*>(p.d_o) + (size_t)b * p.NQ * p.lddo + h * 64;
-    const bf16_t* Oo = reinterpret_cast<const bf16_t*>(p.o) + (size_t)b * p.NQ * p.ldo + h * 64;
-    const bf16_t* K = reinterpret_cast<const bf16_t*>(p.k) + (size_t)b * p.NK * p.ldk + h * 64;
-    const bf16_t* V = reinterpret_cast<const bf16_t*>(p.v) + (size_t)b * p.NK * p.ldv + h * 64;
+    const BwdBase bb(p, b, h);
+    const bf16_t *Q = bb.Q, *G = bb.G, *Oo = bb.Oo, *K = bb.K, *V = bb.V;
     const float* L = p.lse + ((size_t)b * p.H + h) * p.NQ;
     const float* Dl = p.delta + ((size_t)b * p.H + h) * p.NQ;
     ChunkDma<> lq, lg;
@@ -773,16 +725,15 @@ __device__ __forceinline__ void bwd_dkv_block(const AttnParams& p, char* smem, i
     const int nchunks = (p.NQ + CHUNK - 1) / CHUNK;
     // keep bits of (the chunk's 256 queries) x (this workgroup's 2 key tiles): 16 B per query = 4 KiB per chunk = four 1-KiB DMA
     // pieces issued by waves 0-3 (always, see the dQ kernel); piece `wave`, lane l -> query 64 wave + l of the chunk
-    const bool use_bits = p.drop.thresh && p.dmask != nullptr;
-    const int mtiles = mebt_attn_dmask_tiles(p.NK);
-    const size_t mrow0 = ((size_t)b * p.H + h) * p.NQ;
-    const __amdgpu_buffer_rsrc_t rmask = make_rsrc(p.dmask ? p.dmask + mrow0 * mtiles * 4 : (const uint16_t*)p.q, use_bits ? (size_t)p.NQ * mtiles * 8 : 0);
+    const KeepBits km(p, b, h);
+    const bool use_bits = km.use;
+    const int mtiles = km.mtiles;
     const uint32_t moff = (uint32_t)((64 * (wave & 3) + lane) * mtiles * 8 + xb * 16);
     auto issue = [&](char* stage, int chunk) {
         lq.issue(stage, chunk, wave);
         lg.issue(stage + CHUNK_BYTES, chunk, wave);
         if (wave < NSTAT) dma16(rstat, lds_addr_of(stage + 2 * CHUNK_BYTES + wave * STAT_BYTES), (uint32_t)(chunk * CHUNK * 4 + lane * 16));
-        if (wave < 4) dma16(rmask, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * CHUNK * (uint32_t)mtiles * 8);
+        if (wave < 4) dma16(km.rsrc, lds_addr_of(stage + MASK_OFF + wave * 1024), moff + (uint32_t)chunk * CHUNK * (uint32_t)mtiles * 8);
     };
     bf16x8 kf[2], vf[2];
 #pragma unroll
@@ -956,18 +907,30 @@ int launch_attn_block_order_probe(int T, int X, int H, int xcd, int32_t* pos_to_
     return MEBT_OK;
 }
 
+// The forward forms: what launch_attn_fwd_mfma chooses among, and what the launch hook reports of the choice.
+struct FwdForm {
+    void (*kernel)(const AttnParams);
+    int waves, stages, split;       // as reported by mebt_debug_attn_last_launch (split: 0 none, 1 anti-phase groups, 2 groups in phase)
+    int threads, ring_bytes;        // workgroup size; LDS of the K / V rings (a gathered key set adds its index list)
+};
+enum { FWD_8x2, FWD_8x1, FWD_4x2, FWD_4x4, FWD_4x2_SPLIT, FWD_PP };
+static const FwdForm kFwdForms[] = {
+    {attn_fwd_mfma<8, 2>, 8, 2, 0, 512, 4 * CHUNK_BYTES},
+    {attn_fwd_mfma<8, 1>, 8, 1, 0, 512, 2 * CHUNK_BYTES},
+    {attn_fwd_mfma<4, 2>, 4, 2, 0, 256, 2 * CHUNK_BYTES},
+    {attn_fwd_mfma<4, 4>, 4, 4, 0, 256, 4 * CHUNK_BYTES},
+    {attn_fwd_mfma<4, 2, 2>, 4, 2, 2, 512, 4 * CHUNK_BYTES},
+    {attn_fwd_pp, 4, 2, 1, 512, 4 * CHUNK_BYTES},
+};
+
 static int check_layout(const AttnParams& p) {
     if (p.HD != 64) { mebt_set_error("mfma attention: head size must be 64"); return MEBT_ESHAPE; }
     if ((p.ldq | p.ldk | p.ldv | p.ldo) % 8) { mebt_set_error("mfma attention: row strides must be multiples of 8 elements"); return MEBT_ESHAPE; }
     static bool inited = false;
     if (!inited) {
         // the forward kernels may carry a key index list behind their rings (AttnParams::kidx): the whole LDS is admissible
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma<8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma<8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_mfma<4, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_pp), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (const FwdForm& f : kFwdForms)
+            MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(f.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
         MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LDS));
@@ -981,9 +944,9 @@ static int lds_bytes(int streamed_rows) { return streamed_rows <= CHUNK ? STAGE_
 // The forward form of the most recent launch, for the tests (mebt_debug_attn_last_launch): which kernel a shape really selected.
 static int g_fwd_launch_count = 0;
 static int32_t g_fwd_last_launch[4] = {0, 0, 0, 0};
-static void note_fwd_launch(int waves, int stages, int split, dim3 grid) {
+static void note_fwd_launch(const FwdForm& f, dim3 grid) {
     ++g_fwd_launch_count;
-    const int32_t rec[4] = {waves, stages, split, (int32_t)grid.x};
+    const int32_t rec[4] = {f.waves, f.stages, f.split, (int32_t)grid.x};
     memcpy(g_fwd_last_launch, rec, sizeof rec);
 }
 extern "C" int32_t mebt_debug_attn_last_launch(int32_t out[4]) {
@@ -1008,27 +971,21 @@ int launch_attn_fwd_mfma(const AttnParams& p_in, hipStream_t stream) {
     const bool four = force ? force == 4 : grid8 <= 128;
     const int xl = p.kidx ? ((p.NK * 4 + 15) & ~15) : 0;       // the key index list of a sample, staged behind the rings
     if (xl && xl + 4 * CHUNK_BYTES > 160 * 1024) { mebt_set_error("mfma attention: a gathered key set holds at most 8192 keys"); return MEBT_ESHAPE; }
+    const int rows = four ? 64 : BLOCK_ROWS;
+    const dim3 grid((p.NQ + rows - 1) / rows * p.H * p.B);
+    int form;
     if (four) {
-        const dim3 grid((p.NQ + 63) / 64 * p.H * p.B);
         // short key sets: two stages of 128 keys (64 KiB: two workgroups per CU); long ones: four stages, one workgroup per CU
         static const int split_on = [] { const char* e = getenv("MEBT_ATTN_FWD_SPLIT"); return e ? atoi(e) : 1; }();
-        if (p.NK <= 1024) {
-            hipLaunchKernelGGL((attn_fwd_mfma<4, 2>), grid, dim3(256), 2 * CHUNK_BYTES + xl, stream, p);
-            note_fwd_launch(4, 2, 0, grid);
-        } else if (split_on && (long)grid.x <= 256) {    // one workgroup per CU at most: a second group of waves per query block
-            if (split_on == 2) hipLaunchKernelGGL((attn_fwd_mfma<4, 2, 2>), grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);   // both groups in phase (A/B)
-            else hipLaunchKernelGGL(attn_fwd_pp, grid, dim3(512), 4 * CHUNK_BYTES + xl, stream, p);
-            note_fwd_launch(4, 2, split_on == 2 ? 2 : 1, grid);
-        } else {
-            hipLaunchKernelGGL((attn_fwd_mfma<4, 4>), grid, dim3(256), 4 * CHUNK_BYTES + xl, stream, p);
-            note_fwd_launch(4, 4, 0, grid);
-        }
+        if (p.NK <= 1024) form = FWD_4x2;
+        else if (split_on && (long)grid.x <= 256) form = split_on == 2 ? FWD_4x2_SPLIT : FWD_PP;    // one workgroup per CU at most: a second group of waves per query block (2: both groups in phase, A/B)
+        else form = FWD_4x4;
     } else {
-        const dim3 grid((p.NQ + BLOCK_ROWS - 1) / BLOCK_ROWS * p.H * p.B);
-        if (p.NK <= CHUNK) hipLaunchKernelGGL((attn_fwd_mfma<8, 1>), grid, dim3(WAVES * 64), 2 * CHUNK_BYTES + xl, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_mfma<8, 2>), grid, dim3(WAVES * 64), 2 * 2 * CHUNK_BYTES + xl, stream, p);
-        note_fwd_launch(8, p.NK <= CHUNK ? 1 : 2, 0, grid);
+        form = p.NK <= CHUNK ? FWD_8x1 : FWD_8x2;
     }
+    const FwdForm& f = kFwdForms[form];
+    hipLaunchKernelGGL(f.kernel, grid, dim3(f.threads), f.ring_bytes + xl, stream, p);
+    note_fwd_launch(f, grid);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
