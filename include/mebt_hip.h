@@ -370,6 +370,33 @@ int mebt_op_pack_to_clip_u8(const uint8_t* pack, int64_t F, const int64_t* ids, 
  * alignment (rows of a larger store start at multiples of 3 T H W bytes). */
 int mebt_op_video_to_clip_u8(const float* in, uint8_t* out, int32_t B, int32_t Td, int32_t T, int32_t H, int32_t W,
                              mebt_stream_t stream);
+/* ---- reconstruction metrics of the first stage (reference VQGAN.validation_step, mebt/vqgan.py:190-196; codebook.py:64,93-94) ------
+ * The sums behind val/recon_loss, val/commitment_loss, val/perplexity and the per-frame PSNR / SSIM of a reconstruction.  Results are
+ * bitwise reproducible: every floating-point sum is taken per workgroup, written as an fp64 partial into the caller's `scratch` and
+ * added by a second kernel in a fixed order (no float atomics); integer sums are exact in any order.  All offsets are 64-bit.  `scratch`
+ * needs 8-byte alignment and at least the stated number of bytes (`scratch_bytes` is checked before anything is launched). */
+#define MEBT_RECON_ABS_CHUNK 16384      /* elements of one clip per workgroup: 256 lanes x 64 terms */
+#define MEBT_RECON_TILE_H 16            /* SSIM positions per workgroup: 16 rows x 32 columns */
+#define MEBT_RECON_TILE_W 32
+#define MEBT_RECON_CODE_ROWS 16         /* rows of z per workgroup */
+/* out[b] = sum_i |x[b, i] - y[b, i]|, fp64; x, y fp32 [B, n] contiguous (a video and its decode, n = 3 T H W).  A lane adds at most 64
+ * terms in fp32 before the partial is widened to fp64.  scratch: 8 * B * ceil(n / MEBT_RECON_ABS_CHUNK) bytes. */
+int mebt_op_abs_diff_sum(const float* x, const float* y, double* out, int32_t B, int64_t n, void* scratch, int64_t scratch_bytes,
+                         mebt_stream_t stream);
+/* a, b: uint8 [N, H, W, 3], frames of two clips in the layout of mebt_op_i3d_preprocess.  sq_err[n] = sum (a - b)^2 over the frame
+ * (int64, exact); ssim[n] (fp64) = the frame's mean SSIM (Wang et al. 2004): 11 x 11 Gaussian window, sigma 1.5 (g_i = exp(-(i - 5)^2 /
+ * 4.5), normalised in fp64 on the host), valid positions only ((H - 10) x (W - 10), no padding), per channel on the byte values,
+ * C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2, mean over positions and the three channels.  The moments are taken in fp32 on u - 128
+ * (variances are shift invariant) with the window applied as two separable passes through LDS.  H, W >= 11, else
+ * MEBT_STATUS_ESHAPE.  scratch: 16 * N * ceil((H - 10) / MEBT_RECON_TILE_H) * ceil((W - 10) / MEBT_RECON_TILE_W) bytes. */
+int mebt_op_clip_quality_u8(const uint8_t* a, const uint8_t* b, int64_t* sq_err, double* ssim, int32_t N, int32_t H, int32_t W,
+                            void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+/* ids int64 [M], z fp32 [M, d] (the activations the codebook search read), embeddings fp32 [n_codes, d].  hist int64 [n_codes] +=
+ * the number of rows with each id (64-bit integer atomics: the caller zeroes it once and a data set accumulates over calls);
+ * sq_sum[0] (fp64) = sum_m |z_m - e_ids[m]|^2 of this call.  A row whose id is outside [0, n_codes) counts for neither and its
+ * embedding is never read.  scratch: 8 * ceil(M / MEBT_RECON_CODE_ROWS) bytes. */
+int mebt_op_code_stats(const int64_t* ids, const float* z, const float* embeddings, int64_t* hist, double* sq_sum, int64_t M,
+                       int32_t n_codes, int32_t d, void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

@@ -90,6 +90,9 @@ PROTOTYPES = {
     "mebt_op_pack_to_video": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mebt_op_pack_to_clip_u8": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mebt_op_video_to_clip_u8": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mebt_op_abs_diff_sum": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
+    "mebt_op_clip_quality_u8": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_op_code_stats": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mebt_debug_dropout_mask": (c_i32, [C.c_uint64, C.c_uint32, c_f32, c_i64, c_vp, c_vp]),
     "mebt_debug_clock_probe": (c_i32, [c_vp, C.c_uint64, c_vp]),
     "mebt_debug_side_stream": (None, [c_vp, c_i32]),

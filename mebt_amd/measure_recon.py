@@ -1,0 +1,133 @@
+"""`python -m mebt_amd.measure_recon` — how good is a first-stage checkpoint on a data set: the reference's three validation figures
+(`VQGAN.validation_step`, mebt/vqgan.py:190-196: recon_loss, commitment_loss, perplexity) plus the reconstruction's PSNR, SSIM and, with
+`--compute_fvd`, rFVD / rKVD (FVD / KVD between the real clips and their own reconstructions: the floor under every sample's FVD).
+
+Flags: the data flags of VideoData (as `mebt_amd.measure_fvd` takes them), `--vqgan_ckpt`, `--n_sample` (2048), `--train`,
+`--packed_path`, `--vqgan_dtype {f16,f32}`, `--seed`, `--out FILE.csv`, `--save_np FILE.npy` (the reconstructed uint8 clips
+[N, T, H, W, 3]) and `--compute_fvd` with the I3D flags of measure_fvd (`--i3d_ckpt --i3d_dtype --i3d_batch`).
+
+Real side: `--image_folder` with `--data_path` a frame folder (train.txt under `--train`, else test.txt) is read through
+`VideoData(..., raw=True)`: the workers only decode, crop / resize / normalisation run in the frame-ingest kernel; with
+`--packed_path DIR` the folder's pack is gathered on the GPU instead (the same bytes in the same order).  Otherwise `--data_path` names
+a uint8 [N, T, H, W, C] .npy of square clips.  One seeded pass over the split in batches of `--batch_size`, cut at `--n_sample` clips; a
+split that ends sooner ends the run there and the count is printed.  Every batch gives the float clip for the encoder and the byte
+clip for the metrics on the device; the clips, their reconstructions and every sum stay in HBM (mebt_amd/recon.py), one row of scalars
+is read back at the end.
+
+Output: one CSV row (pandas' to_csv layout, `measure_fvd.write_csv`) with the columns of `recon.FIELDS` (+ rFVD, rKVD), also printed.
+"""
+import argparse
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+from .data import TokenData
+from .measure_fvd import add_scoring_args, frame_folder, write_csv
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="reconstruction quality of a 3D-VQGAN checkpoint: recon loss, commitment loss, perplexity, "
+                                                 "PSNR, SSIM and (--compute_fvd) rFVD / rKVD")
+    parser = TokenData.add_data_specific_args(parser)
+    parser.add_argument('--vqgan_ckpt', type=str, default='')
+    parser.add_argument('--n_sample', type=int, default=2048)
+    parser.add_argument('--vqgan_dtype', type=str, default='f16', choices=['f16', 'f32'])
+    parser.add_argument('--seed', type=int, default=0, help='seeds the one pass over the split (shuffle and start frames)')
+    parser.add_argument('--out', type=str, default='recon.csv', help='the CSV the row is written to')
+    parser.add_argument('--save_np', type=str, default='', help='.npy for the reconstructed uint8 clips [N, T, H, W, 3]')
+    return add_scoring_args(parser)              # --train --packed_path --compute_fvd --i3d_ckpt --i3d_dtype --i3d_batch
+
+
+def seed_everything(seed):
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+def real_batches(args, device):
+    """(float clip [B, 3, T, R, R], byte clip [B, T, R, R, 3]) pairs on the device, one pass over the split"""
+    if frame_folder(args):
+        from .config import AttrDict
+        from .data import VideoData
+        if args.sequence_length < 1:
+            raise SystemExit(f'--sequence_length {args.sequence_length}: whole-video clips differ in length and do not stack')
+        data = VideoData(AttrDict(vars(args)), True, raw=True)
+        for batch in (data.train_dataloader() if args.train else data.val_dataloader()):
+            raw = batch['video'].to(device, non_blocking=True)
+            yield raw.to_video(), raw.to_clip_u8()
+        return
+    path = args.data_path
+    if not (path.endswith('.npy') and os.path.isfile(path)):
+        raise SystemExit(f"--data_path {path!r}: expected a frame folder (--image_folder with a directory holding train.txt under --train, "
+                         "else test.txt) or a uint8 [N, T, H, W, C] .npy of real clips")
+    from .packed import pack_to_clip_u8, pack_to_video
+    real = np.load(path, mmap_mode='r')
+    if real.dtype != np.uint8 or real.ndim != 5 or real.shape[-1] != 3 or real.shape[2] != real.shape[3]:
+        raise SystemExit(f'--data_path {path}: expected uint8 [N, T, R, R, 3], got {real.dtype} {real.shape}')
+    T, R = args.sequence_length, int(real.shape[2])
+    if real.shape[1] < T:
+        raise SystemExit(f'--data_path {path}: clips of {real.shape[1]} frames, shorter than --sequence_length {T}')
+    order = torch.randperm(len(real)).tolist()
+    for i in range(0, len(order), args.batch_size):
+        rows = sorted(order[i:i + args.batch_size])
+        u8 = torch.from_numpy(np.ascontiguousarray(real[rows, :T])).to(device)
+        ids = torch.arange(len(rows) * T, device=device).view(len(rows), T)
+        pack = u8.view(-1, R, R, 3)
+        yield pack_to_video(pack, ids, R), pack_to_clip_u8(pack, ids, R)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    print(args)
+    from . import recon
+    from .vqgan import load_vqgan
+    device = torch.device('cuda')
+    vqgan = load_vqgan(args.vqgan_ckpt, device)
+    vqgan.compute_dtype = args.vqgan_dtype
+    print(f'VQGAN compute dtype: {args.vqgan_dtype}')
+    i3d = None
+    if args.compute_fvd:
+        from .fvd import frechet_distance, get_fvd_logits, polynomial_mmd
+        from .measure_fvd import load_model
+        i3d = load_model(args, device)
+    seed_everything(args.seed)
+    acc = recon.ReconAccumulator(vqgan.n_codes, l1_weight=vqgan._hp("l1_weight", 4.0), device=device)
+    saved, emb_real, emb_fake = [], [], []
+    for x, u8 in real_batches(args, device):
+        left = args.n_sample - acc.n_clips
+        if len(x) > left:
+            x, u8 = x[:left].contiguous(), u8[:left].contiguous()
+        st = vqgan.reconstruct_stats(x, clip_u8=u8)
+        acc.add(st)
+        if args.save_np:
+            saved.append(st["recon_u8"])
+        if i3d is not None:
+            emb_real.append(get_fvd_logits(u8, i3d=i3d, device=device, batch=args.i3d_batch))
+            emb_fake.append(get_fvd_logits(st["recon_u8"], i3d=i3d, device=device, batch=args.i3d_batch))
+        if acc.n_clips >= args.n_sample:
+            break
+    if acc.n_clips == 0:
+        raise SystemExit(f'--data_path {args.data_path}: the {"train" if args.train else "test"} split gave no clip')
+    if acc.n_clips < args.n_sample:
+        print(f'the split ended after {acc.n_clips} clips, fewer than --n_sample {args.n_sample}')
+    row = acc.result()
+    columns = list(recon.FIELDS)
+    if i3d is not None:
+        real, fake = torch.cat(emb_real, 0), torch.cat(emb_fake, 0)
+        row["rFVD"], row["rKVD"] = float(frechet_distance(fake, real)), float(polynomial_mmd(fake, real))
+        columns += ["rFVD", "rKVD"]
+    if args.save_np:
+        np.save(args.save_np, torch.cat(saved, 0).cpu().numpy())
+        print(f'wrote {acc.n_clips} reconstructed clips to {args.save_np}')
+    write_csv(args.out, columns, [[row[c] for c in columns]])
+    print(','.join(columns))
+    print(','.join(repr(row[c]) for c in columns))
+    print(f'wrote {args.out}')
+    return row
+
+
+if __name__ == '__main__':
+    main(sys.argv[1:])

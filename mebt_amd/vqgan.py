@@ -2,8 +2,9 @@
 operators of csrc/vqgan.hip.  Same constructor argument (`args` namespace with n_hiddens / downsample / image_channels /
 embedding_dim / n_codes), module tree and state-dict names (`encoder.conv_first.conv.weight`, `encoder.conv_blocks.0.res.norm1.weight`,
 `decoder.conv_blocks.0.up.convt.weight`, `pre_vq_conv.conv.weight`, `codebook.embeddings`, ...) so reference checkpoints load;
-the discriminators / LPIPS / losses (training of the first stage, SURVEY.md §2 OUT-OF-SCOPE) are not built and their keys are
-ignored on load.
+the discriminators / LPIPS / training losses (training of the first stage, SURVEY.md §2 OUT-OF-SCOPE) are not built and their keys are
+ignored on load.  `validation_step` (vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric
+operators of csrc/recon/recon.hip (mebt_amd/recon.py).
 
 The nn.Modules below only HOLD parameters.  `encode` / `decode` walk a launch plan: every convolution is one
 `mebt_op_conv3d` call per output sub-lattice (1 for a convolution, 4 or 8 for a stride-2 transposed convolution), every
@@ -374,6 +375,58 @@ class VQGAN(nn.Module):
     def forward(self, x):
         """reconstruction (the inference part of vqgan.py:95-100): decode(encode(x))"""
         return self.decode(self.encode(x))
+
+    # ---- validation (vqgan.py:190-196) on the metric operators of csrc/recon/recon.hip ---------------------------------------------------
+    def _hp(self, name, default):
+        a = self.args
+        return a.get(name, default) if isinstance(a, dict) else getattr(a, name, default)
+
+    def log(self, name, value, **kwargs):
+        """pl.LightningModule.log for a module that runs without a trainer: the last value of every name, in `self.logged`"""
+        self.__dict__.setdefault("logged", {})[name] = value
+
+    @torch.no_grad()
+    def reconstruct_stats(self, x, clip_u8=None):
+        """x float32 [B, 3, T, H, W] on the GPU -> the reconstruction and the sums its quality figures are made of, all on the device:
+        `recon` (decode(encode(x))), `ids`, `abs_sum` [B] = sum |recon - x|, `hist` [n_codes] of this batch's ids, `commit_sq_sum` [1] =
+        sum |z - e|^2, `sq_err` / `ssim` [B, T] per frame of the byte clips `real_u8` / `recon_u8` [B, T, H, W, 3].  The bytes of both sides
+        are `frames.video_to_clip_u8`'s, what the sampling scripts save and FVD reads; `clip_u8` hands in the real side's when the
+        caller has them already (a raw batch's `to_clip_u8()`: the same bytes).  `frame_bytes` and `z_values` are the element counts
+        the means divide by."""
+        from . import recon
+        from .frames import video_to_clip_u8
+        x = x.to(torch.float32).contiguous()
+        B = x.shape[0]
+        ids = self.encode(x)
+        z = self._last_z
+        rec = self.decode(ids)
+        hist, sq_sum = recon.code_stats(ids, z, self._prepared["emb"])
+        real_u8 = video_to_clip_u8(x) if clip_u8 is None else clip_u8
+        recon_u8 = video_to_clip_u8(rec)
+        sq_err, ssim = recon.clip_quality_u8(real_u8, recon_u8)
+        return {"recon": rec, "ids": ids, "abs_sum": recon.abs_diff_sum(x.view(B, -1), rec.view(B, -1)), "hist": hist,
+                "commit_sq_sum": sq_sum, "sq_err": sq_err, "ssim": ssim, "real_u8": real_u8, "recon_u8": recon_u8,
+                "frame_bytes": int(np.prod(real_u8.shape[2:])), "z_values": z.numel()}
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """VQGAN.validation_step (vqgan.py:190-196): logs and returns val/recon_loss = mean |x_recon - x| * l1_weight, val/commitment_loss
+        = 0.25 * mean (z - e)^2 and val/perplexity of the batch (0-dim float64 tensors on the device).  The perceptual term needs LPIPS'
+        VGG weights, which are not built: it is logged as 0 when perceptual_weight is 0 (the reference's default) and left out otherwise."""
+        from . import recon
+        from .frames import to_device_video
+        x = to_device_video(batch["video"], self.codebook.embeddings.device)
+        st = self.reconstruct_stats(x)
+        out = {"val/recon_loss": st["abs_sum"].sum() / st["recon"].numel() * float(self._hp("l1_weight", 4.0)),
+               "val/commitment_loss": 0.25 * st["commit_sq_sum"][0] / st["z_values"],
+               "val/perplexity": recon.perplexity_of(st["hist"])}
+        if float(self._hp("perceptual_weight", 0.0)) == 0.0:
+            out["val/perceptual_loss"] = torch.zeros((), device=x.device, dtype=torch.float64)
+        else:
+            print("validation_step: val/perceptual_loss is left out (LPIPS is not built)")
+        for k, v in out.items():
+            self.log(k, v, prog_bar=True)
+        return out
 
 
 def load_vqgan(vqgan_ckpt, device=torch.device('cpu')):
