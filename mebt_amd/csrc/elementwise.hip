@@ -4,6 +4,7 @@
 // per-row statistics).
 #include "common.h"
 #include <cstdlib>
+#include <type_traits>
 #include "kernels.h"
 
 namespace {
@@ -93,6 +94,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const EmbedBwdParams p) 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm
 // ------------------------------------------------------------------------------------------------
+// One wave per row, 4 rows per workgroup; a launch takes several jobs, whose workgroups are enumerated by the block id.
 constexpr int LN_MAXC = 8;   // d <= 2048
 
 __device__ __forceinline__ long map_row(long r, int seg, int seg_stride, int seg_off) {
@@ -102,137 +104,16 @@ __device__ __forceinline__ long map_row(long r, int seg, int seg_stride, int seg
 struct LnFwdMulti { LnFwdParams j[MEBT_LN_MAXJ]; int blk_start[MEBT_LN_MAXJ + 1]; int n; };
 struct LnBwdMulti { LnBwdParams j[MEBT_LN_MAXJ]; int blk_start[MEBT_LN_MAXJ + 1]; int rpw[MEBT_LN_MAXJ]; int n; };
 
-// one wave per row, 4 rows per workgroup; the workgroups of all jobs are enumerated by blockIdx.x
-template <typename T>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdMulti mj) {
+// which of the n jobs (workgroups [blk_start[i], blk_start[i + 1])) owns workgroup `bid`
+template <int MAXJ>
+__device__ __forceinline__ int find_job(const int (&blk_start)[MAXJ + 1], int n, int bid) {
     int job = 0;
 #pragma unroll
-    for (int i = 1; i < MEBT_LN_MAXJ; ++i)
-        if (i < mj.n && (int)blockIdx.x >= mj.blk_start[i]) job = i;
-    const LnFwdParams& p = mj.j[job];
-    const int lane = threadIdx.x & 63;
-    const long row = (long)(blockIdx.x - mj.blk_start[job]) * 4 + (threadIdx.x >> 6);
-    if (row >= p.rows) return;
-    const T* x = reinterpret_cast<const T*>(p.x) + (size_t)row * p.d;
-    f32x4 v[LN_MAXC];
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-        const int e = lane * 4 + 256 * c;
-        if (e < p.d) {
-            v[c] = load4<T>(x + e);
-            s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
-        }
-    }
-    const float mean = wave_sum(s) / p.d;
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-        const int e = lane * 4 + 256 * c;
-        if (e < p.d) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const float t = v[c][j] - mean; q += t * t; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / p.d + 1e-5f);
-    const long orow = map_row(row, p.seg, p.seg_stride, p.seg_off);
-    T* y = reinterpret_cast<T*>(p.y) + (size_t)orow * p.d;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-        const int e = lane * 4 + 256 * c;
-        if (e < p.d) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(p.gamma + e);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(p.beta + e);
-            f32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = (v[c][j] - mean) * rstd * g[j] + b[j];
-            store4<T>(y + e, o);
-        }
-    }
-    if (p.mean && lane == 0) { p.mean[orow] = mean; p.rstd[orow] = rstd; }
+    for (int i = 1; i < MAXJ; ++i)
+        if (i < n && bid >= blk_start[i]) job = i;
+    return job;
 }
 
-// LayerNorm backward, two kernels (each takes several jobs per launch):
-//  (1) dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) [+ dx_add] (+ optional dropout'd copy dx2)
-//      — one wave per row, 4 rows per workgroup;
-//  (2) dgamma += sum_rows dy*xhat, dbeta += sum_rows dy — column reduction (64 columns x a chunk of
-//      rows per workgroup, LDS reduce, ONE atomic per column per workgroup: float atomics collapse
-//      when hundreds of workgroups meet on the same 2*d addresses — a fused variant with one adder per
-//      16 rows ran 4x slower than both kernels together).
-template <typename T>
-__device__ __forceinline__ void ln_bwd_dx_body(const LnBwdMulti& mj, int bid) {
-    int job = 0;
-#pragma unroll
-    for (int i = 1; i < MEBT_LN_MAXJ; ++i)
-        if (i < mj.n && bid >= mj.blk_start[i]) job = i;
-    const LnBwdParams& p = mj.j[job];
-    const int lane = threadIdx.x & 63;
-    const int d = p.d;
-    const long row = (long)(bid - mj.blk_start[job]) * 4 + (threadIdx.x >> 6);
-    if (row >= p.rows) return;
-    const long mrow = map_row(row, p.seg, p.seg_stride, p.seg_off);
-    const T* x = reinterpret_cast<const T*>(p.x) + (size_t)row * d;
-    const T* dy = reinterpret_cast<const T*>(p.dy) + (size_t)mrow * d;
-    const T* dy2 = p.dy2 ? reinterpret_cast<const T*>(p.dy2) + (size_t)row * d : nullptr;
-    const float mean = p.mean[mrow], rstd = p.rstd[mrow];
-    f32x4 xh[LN_MAXC], gy[LN_MAXC];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-        const int e = lane * 4 + 256 * c;
-        if (e < d) {
-            const f32x4 xv = load4<T>(x + e);
-            f32x4 dv = load4<T>(dy + e);
-            if (dy2) dv += load4<T>(dy2 + e);
-            const f32x4 g = *reinterpret_cast<const f32x4*>(p.gamma + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                xh[c][j] = (xv[j] - mean) * rstd;
-                gy[c][j] = dv[j] * g[j];
-                s1 += gy[c][j];
-                s2 += gy[c][j] * xh[c][j];
-            }
-        }
-    }
-    const float m1 = wave_sum(s1) / d, m2 = wave_sum(s2) / d;
-    const bool f32out = sizeof(T) == 4 || p.dx_f32;           // job-uniform: fp32 gradient accumulators (contexts) or T
-#pragma unroll
-    for (int c = 0; c < LN_MAXC; ++c) {
-        const int e = lane * 4 + 256 * c;
-        if (e < d) {
-            f32x4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = rstd * (gy[c][j] - m1 - xh[c][j] * m2);
-            if (p.dx_add) o += load4<T>(reinterpret_cast<const T*>(p.dx_add) + (size_t)row * d + e);
-            const size_t oi = (size_t)row * d + e;
-            if (f32out) {
-                float* dx = reinterpret_cast<float*>(p.dx) + oi;
-                if (p.dx_accumulate) o += load4<float>(dx);
-                store4<float>(dx, o);
-            } else {
-                T* dx = reinterpret_cast<T*>(p.dx) + oi;
-                if (p.dx_accumulate) o += load4<T>(dx);
-                store4<T>(dx, o);
-            }
-            if (p.dx2) {
-                f32x4 m = o;                        // mask the value as stored (rounded to the type of dx)
-                if (!f32out) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) m[j] = (float)(T)o[j];
-                }
-                m *= drop_keep4(p.drop2, (uint64_t)oi);
-                if (f32out) store4<float>(reinterpret_cast<float*>(p.dx2) + oi, m);
-                else store4<T>(reinterpret_cast<T*>(p.dx2) + oi, m);
-            }
-        }
-    }
-}
-
-// ---- fast paths: d == NCH * 64 * V with V = 16 bytes of T per lane -------------------------------------
-// The generic kernels above guard every 256-element chunk with `e < d` (runtime d): hipcc then branches
-// around each load and waits for it (s_waitcnt vmcnt(0) per chunk), i.e. the row is fetched as a chain of
-// dependent round trips (1.5 TB/s measured).  With the chunk count a template parameter every load of
-// the row is issued before the first use.
 template <typename T> struct LaneVec;
 template <> struct LaneVec<float> { static constexpr int V = 4; };
 template <> struct LaneVec<bf16_t> { static constexpr int V = 8; };
@@ -242,6 +123,11 @@ template <> __device__ __forceinline__ void loadv<float, 4>(const float* p, floa
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = v[j];
 }
+template <> __device__ __forceinline__ void loadv<bf16_t, 4>(const bf16_t* p, float (&o)[4]) {
+    const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = (float)v[j];
+}
 template <> __device__ __forceinline__ void loadv<bf16_t, 8>(const bf16_t* p, float (&o)[8]) {
     const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
 #pragma unroll
@@ -250,6 +136,9 @@ template <> __device__ __forceinline__ void loadv<bf16_t, 8>(const bf16_t* p, fl
 template <typename T, int V> __device__ __forceinline__ void storev(T* p, const float (&o)[V]);
 template <> __device__ __forceinline__ void storev<float, 4>(float* p, const float (&o)[4]) {
     *reinterpret_cast<f32x4*>(p) = f32x4{o[0], o[1], o[2], o[3]};
+}
+template <> __device__ __forceinline__ void storev<bf16_t, 4>(bf16_t* p, const float (&o)[4]) {
+    *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16_t)o[0], (bf16_t)o[1], (bf16_t)o[2], (bf16_t)o[3]};
 }
 template <> __device__ __forceinline__ void storev<bf16_t, 8>(bf16_t* p, const float (&o)[8]) {
     bf16x8 v;
@@ -270,131 +159,228 @@ template <int V> __device__ __forceinline__ void storef(float* p, const float (&
     for (int q = 0; q < V / 4; ++q) *reinterpret_cast<f32x4*>(p + 4 * q) = f32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
 }
 
-template <typename T, int NCH>
-__global__ __launch_bounds__(256) void ln_fwd_fast_kernel(const LnFwdMulti mj) {
-    constexpr int V = LaneVec<T>::V, D = NCH * 64 * V;
-    int job = 0;
+// How a wave covers a row: lane l holds elements [c * 64 * V + l * V, + V) of chunk c.
+//  NCH > 0: d == NCH * 64 * V with V = 16 bytes of T per lane, every chunk live.  With a runtime guard around a chunk hipcc
+//           branches around each load and waits for it (s_waitcnt vmcnt(0) per chunk), i.e. the row is fetched as a chain of
+//           dependent round trips (1.5 TB/s measured); with the chunk count a template parameter there is no guard and every
+//           load of the row is issued before the first use.  These are the widths of LN_WIDTHS below.
+//  NCH == 0: any d % 4 == 0 up to 256 * LN_MAXC, 4 elements per lane and chunk, the chunks beyond d skipped.
+template <typename T, int NCH> struct LnRow {
+    static constexpr bool FIXED = NCH > 0;
+    static constexpr int V = FIXED ? LaneVec<T>::V : 4;
+    static constexpr int NC = FIXED ? NCH : LN_MAXC;
+    int d_;
+    __device__ __forceinline__ int d() const { if constexpr (FIXED) return NC * 64 * V; else return d_; }
+    __device__ __forceinline__ bool live(int c, int lane) const { if constexpr (FIXED) return true; else return c * 64 * V + lane * V < d_; }
+    // lane partial of the row sum; the generic form adds a chunk's four elements first, as it always has
+    static __device__ __forceinline__ float add(float s, const float (&v)[V]) {
+        if constexpr (FIXED) {
 #pragma unroll
-    for (int i = 1; i < MEBT_LN_MAXJ; ++i)
-        if (i < mj.n && (int)blockIdx.x >= mj.blk_start[i]) job = i;
+            for (int j = 0; j < V; ++j) s += v[j];
+            return s;
+        } else {
+            return s + (v[0] + v[1] + v[2] + v[3]);
+        }
+    }
+};
+
+template <typename T, int NCH>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdMulti mj) {
+    using Row = LnRow<T, NCH>;
+    constexpr int V = Row::V, NC = Row::NC;
+    const int job = find_job<MEBT_LN_MAXJ>(mj.blk_start, mj.n, blockIdx.x);
     const LnFwdParams& p = mj.j[job];
+    const Row r{p.d};
+    const int d = r.d();
     const int lane = threadIdx.x & 63;
     const long row = (long)(blockIdx.x - mj.blk_start[job]) * 4 + (threadIdx.x >> 6);
     if (row >= p.rows) return;
-    const T* x = reinterpret_cast<const T*>(p.x) + (size_t)row * D + lane * V;
-    float v[NCH][V], g[NCH][V], b[NCH][V];
+    const T* x = reinterpret_cast<const T*>(p.x) + (size_t)row * d + lane * V;
+    float v[NC][V], g[NC][V], b[NC][V];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) loadv<T, V>(x + c * 64 * V, v[c]);
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) loadv<T, V>(x + c * 64 * V, v[c]);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) { loadf<V>(p.gamma + c * 64 * V + lane * V, g[c]); loadf<V>(p.beta + c * 64 * V + lane * V, b[c]); }
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) { loadf<V>(p.gamma + c * 64 * V + lane * V, g[c]); loadf<V>(p.beta + c * 64 * V + lane * V, b[c]); }
     float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int j = 0; j < V; ++j) s += v[c][j];
-    const float mean = wave_sum(s) * (1.0f / D);
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) s = Row::add(s, v[c]);
+    const float mean = wave_sum(s) / d;
     float q = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
 #pragma unroll
-        for (int j = 0; j < V; ++j) { const float t = v[c][j] - mean; q += t * t; }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+            for (int j = 0; j < V; ++j) { const float t = v[c][j] - mean; q += t * t; }
+        }
+    const float rstd = rsqrtf(wave_sum(q) / d + 1e-5f);
     const long orow = map_row(row, p.seg, p.seg_stride, p.seg_off);
-    T* y = reinterpret_cast<T*>(p.y) + (size_t)orow * D + lane * V;
+    T* y = reinterpret_cast<T*>(p.y) + (size_t)orow * d + lane * V;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        float o[V];
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
+            float o[V];
 #pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = (v[c][j] - mean) * rstd * g[c][j] + b[c][j];
-        storev<T, V>(y + c * 64 * V, o);
-    }
+            for (int j = 0; j < V; ++j) o[j] = (v[c][j] - mean) * rstd * g[c][j] + b[c][j];
+            storev<T, V>(y + c * 64 * V, o);
+        }
     if (p.mean && lane == 0) { p.mean[orow] = mean; p.rstd[orow] = rstd; }
 }
 
+// LayerNorm backward, two parts (each takes several jobs per launch):
+//  (1) dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) + (dx_add + old dx) (+ optional dropout'd copy dx2)
+//      — one wave per row, 4 rows per workgroup;
+//  (2) dgamma += sum_rows dy*xhat, dbeta += sum_rows dy — column reduction (64 columns x a chunk of
+//      rows per workgroup, LDS reduce, ONE atomic per column per workgroup: float atomics collapse
+//      when hundreds of workgroups meet on the same 2*d addresses — a fused variant with one adder per
+//      16 rows ran 4x slower than both kernels together).
 template <typename T, int NCH>
-__device__ __forceinline__ void ln_bwd_dx_fast_body(const LnBwdMulti& mj, int bid) {
-    constexpr int V = LaneVec<T>::V, D = NCH * 64 * V;
-    int job = 0;
-#pragma unroll
-    for (int i = 1; i < MEBT_LN_MAXJ; ++i)
-        if (i < mj.n && bid >= mj.blk_start[i]) job = i;
+__device__ __forceinline__ void ln_bwd_dx_body(const LnBwdMulti& mj, int bid) {
+    using Row = LnRow<T, NCH>;
+    constexpr int V = Row::V, NC = Row::NC;
+    const int job = find_job<MEBT_LN_MAXJ>(mj.blk_start, mj.n, bid);
     const LnBwdParams& p = mj.j[job];
+    const Row r{p.d};
+    const int d = r.d();
     const int lane = threadIdx.x & 63;
     const long row = (long)(bid - mj.blk_start[job]) * 4 + (threadIdx.x >> 6);
     if (row >= p.rows) return;
     const long mrow = map_row(row, p.seg, p.seg_stride, p.seg_off);
-    const size_t ro = (size_t)row * D + lane * V, mo = (size_t)mrow * D + lane * V;
-    const bool f32out = sizeof(T) == 4 || p.dx_f32;
+    const size_t ro = (size_t)row * d + lane * V, mo = (size_t)mrow * d + lane * V;
+    const bool f32out = sizeof(T) == 4 || p.dx_f32;           // job-uniform: fp32 gradient accumulators (contexts) or T
     // optional operands are loaded unconditionally (from the x row, scaled by 0, when absent): a branch
     // around a load makes hipcc drain the load queue at the join
     const T* dy2p = p.dy2 ? reinterpret_cast<const T*>(p.dy2) + ro : reinterpret_cast<const T*>(p.x) + ro;
     const T* addp = p.dx_add ? reinterpret_cast<const T*>(p.dx_add) + ro : reinterpret_cast<const T*>(p.x) + ro;
     const float k2 = p.dy2 ? 1.f : 0.f, ka = p.dx_add ? 1.f : 0.f;
-    float xv[NCH][V], dv[NCH][V], g[NCH][V], add[NCH][V], d2[NCH][V];
+    float xv[NC][V], dv[NC][V], g[NC][V], add[NC][V], d2[NC][V];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        loadv<T, V>(reinterpret_cast<const T*>(p.x) + ro + c * 64 * V, xv[c]);
-        loadv<T, V>(reinterpret_cast<const T*>(p.dy) + mo + c * 64 * V, dv[c]);
-        loadv<T, V>(dy2p + c * 64 * V, d2[c]);
-        loadv<T, V>(addp + c * 64 * V, add[c]);
-        loadf<V>(p.gamma + c * 64 * V + lane * V, g[c]);
-    }
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
+            loadv<T, V>(reinterpret_cast<const T*>(p.x) + ro + c * 64 * V, xv[c]);
+            loadv<T, V>(reinterpret_cast<const T*>(p.dy) + mo + c * 64 * V, dv[c]);
+            loadv<T, V>(dy2p + c * 64 * V, d2[c]);
+            loadv<T, V>(addp + c * 64 * V, add[c]);
+            loadf<V>(p.gamma + c * 64 * V + lane * V, g[c]);
+        }
     const float mean = p.mean[mrow], rstd = p.rstd[mrow];
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
 #pragma unroll
-        for (int j = 0; j < V; ++j) { dv[c][j] += k2 * d2[c][j]; add[c][j] *= ka; }
+            for (int j = 0; j < V; ++j) { dv[c][j] += k2 * d2[c][j]; add[c][j] *= ka; }
+        }
     if (p.dx_accumulate) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            float t[V];
-            if (f32out) loadf<V>(reinterpret_cast<const float*>(p.dx) + ro + c * 64 * V, t);
-            else loadv<T, V>(reinterpret_cast<const T*>(p.dx) + ro + c * 64 * V, t);
+        for (int c = 0; c < NC; ++c)
+            if (r.live(c, lane)) {
+                float t[V];
+                if (f32out) loadf<V>(reinterpret_cast<const float*>(p.dx) + ro + c * 64 * V, t);
+                else loadv<T, V>(reinterpret_cast<const T*>(p.dx) + ro + c * 64 * V, t);
 #pragma unroll
-            for (int j = 0; j < V; ++j) add[c][j] += t[j];
-        }
+                for (int j = 0; j < V; ++j) add[c][j] += t[j];
+            }
     }
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            xv[c][j] = (xv[c][j] - mean) * rstd;        // xhat
-            dv[c][j] *= g[c][j];                        // dy * gamma
-            s1 += dv[c][j];
-            s2 += dv[c][j] * xv[c][j];
-        }
-    const float m1 = wave_sum(s1) * (1.0f / D), m2 = wave_sum(s2) * (1.0f / D);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        float o[V];
-#pragma unroll
-        for (int j = 0; j < V; ++j) o[j] = rstd * (dv[c][j] - m1 - xv[c][j] * m2) + add[c][j];
-        const size_t oi = ro + c * 64 * V;
-        if (f32out) storef<V>(reinterpret_cast<float*>(p.dx) + oi, o);
-        else storev<T, V>(reinterpret_cast<T*>(p.dx) + oi, o);
-        if (p.dx2) {
-            float m[V];
-#pragma unroll
-            for (int q4 = 0; q4 < V / 4; ++q4) {
-                const f32x4 k4 = drop_keep4(p.drop2, (uint64_t)oi + 4 * q4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) m[4 * q4 + j] = (f32out ? o[4 * q4 + j] : (float)(T)o[4 * q4 + j]) * k4[j];
+            for (int j = 0; j < V; ++j) {
+                xv[c][j] = (xv[c][j] - mean) * rstd;        // xhat
+                dv[c][j] *= g[c][j];                        // dy * gamma
+                s1 += dv[c][j];
+                s2 += dv[c][j] * xv[c][j];
             }
-            if (f32out) storef<V>(reinterpret_cast<float*>(p.dx2) + oi, m);
-            else storev<T, V>(reinterpret_cast<T*>(p.dx2) + oi, m);
         }
+    const float m1 = wave_sum(s1) / d, m2 = wave_sum(s2) / d;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+        if (r.live(c, lane)) {
+            float o[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) o[j] = rstd * (dv[c][j] - m1 - xv[c][j] * m2) + add[c][j];
+            const size_t oi = ro + c * 64 * V;
+            if (f32out) storef<V>(reinterpret_cast<float*>(p.dx) + oi, o);
+            else storev<T, V>(reinterpret_cast<T*>(p.dx) + oi, o);
+            if (p.dx2) {
+                float m[V];                             // mask the value as stored (rounded to the type of dx)
+#pragma unroll
+                for (int q4 = 0; q4 < V / 4; ++q4) {
+                    const f32x4 k4 = drop_keep4(p.drop2, (uint64_t)oi + 4 * q4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) m[4 * q4 + j] = (f32out ? o[4 * q4 + j] : (float)(T)o[4 * q4 + j]) * k4[j];
+                }
+                if (f32out) storef<V>(reinterpret_cast<float*>(p.dx2) + oi, m);
+                else storev<T, V>(reinterpret_cast<T*>(p.dx2) + oi, m);
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------
+// column sums: out[n] += sum_m X[m,n]
+// ------------------------------------------------------------------------------------------------
+// Workgroup = 64 columns x `rpb` rows: thread (cg = tid&15, rl = tid>>4) sums rows rl, rl+16, ... of
+// its 4 columns (16 threads x 8/16 B = one 128/256-B segment per row), the 16 row-lanes are reduced
+// through LDS and ONE atomic per column leaves the workgroup, so at most M/rpb adders meet on an
+// address (float atomics collapse under contention).
+// The tail: NS sums per thread (NS = 2: the dgamma / dbeta pair); sum s of columns col0 + 0..63 is added to out(s)[col0 + 0..63]
+template <int NS, typename Out>
+__device__ __forceinline__ void colsum_reduce_add(const f32x4 (&acc)[NS], Out out, int col0, int N) {
+    __shared__ float red[NS][16][64 + 4];
+    const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) red[s][rl][cg * 4 + j] = acc[s][j];
+    __syncthreads();
+    if (threadIdx.x < 64 * NS) {
+        const int which = threadIdx.x >> 6, col = threadIdx.x & 63;
+        float t = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t += red[which][r][col];
+        const int c = col0 + col;
+        if (c < N) atomicAdd(out(which) + c, t);
     }
 }
 
+// tile (bx, by) of one column sum (the item is read where it is used: it may lie in kernel-argument memory)
+template <typename T>
+__device__ __forceinline__ void colsum_tile(const GroupedColsum::Item& it, int bx, int by) {
+    const T* X = reinterpret_cast<const T*>(it.X);
+    const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int n = bx * 64 + cg * 4;
+    const int m0 = by * it.rpb, m1 = min(it.M, m0 + it.rpb);
+    f32x4 acc = {0, 0, 0, 0};
+    if (n < it.N)
+#pragma unroll 8
+        for (int m = m0 + rl; m < m1; m += 16) acc += load4<T>(X + (size_t)m * it.ldx + n);
+    colsum_reduce_add<1>({acc}, [&](int) { return it.out; }, bx * 64, it.N);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel(const T* X, int M, int N, int ldx, float* out, int rows_per_block) {
+    colsum_tile<T>(GroupedColsum::Item{X, out, M, N, ldx, (int)gridDim.x, rows_per_block}, blockIdx.x, blockIdx.y);
+}
+
+template <typename T>
+__device__ __forceinline__ void colsum_grouped_body(const GroupedColsum& c, int bid) {
+    const int g = find_job<MEBT_MAX_GROUP>(c.blk_start, c.n, bid);
+    const GroupedColsum::Item& it = c.g[g];
+    const int b = bid - c.blk_start[g];
+    colsum_tile<T>(it, b % it.gx, b / it.gx);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_grouped_kernel(const GroupedColsum c) { colsum_grouped_body<T>(c, blockIdx.x); }
+
+// dgamma / dbeta of LayerNorm: the same tile with two sums per thread over mapped rows.
 // blocks of job j: gx = ceil(d/64) column groups x ceil(rows/rpw) row chunks (rpw = rows per workgroup here)
 template <typename T>
 __device__ __forceinline__ void ln_bwd_param_body(const LnBwdMulti& mj, int bid) {
-    __shared__ float red[2][16][64 + 4];
-    int job = 0;
-#pragma unroll
-    for (int i = 1; i < MEBT_LN_MAXJ; ++i)
-        if (i < mj.n && bid >= mj.blk_start[i]) job = i;
+    const int job = find_job<MEBT_LN_MAXJ>(mj.blk_start, mj.n, bid);
     const LnBwdParams& p = mj.j[job];
     const int rows_per_block = mj.rpw[job];
     const int gx = (p.d + 63) / 64;
@@ -416,106 +402,22 @@ __device__ __forceinline__ void ln_bwd_param_body(const LnBwdMulti& mj, int bid)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { ag[j] += dv[j] * ((xv[j] - mean) * rstd); ab[j] += dv[j]; }
         }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { red[0][rl][cg * 4 + j] = ag[j]; red[1][rl][cg * 4 + j] = ab[j]; }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        const int which = threadIdx.x >> 6, col = threadIdx.x & 63;
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += red[which][r][col];
-        const int c = bx * 64 + col;
-        if (c < p.d) atomicAdd((which ? p.dbeta : p.dgamma) + c, t);
-    }
+    colsum_reduce_add<2>({ag, ab}, [&](int which) { return which ? p.dbeta : p.dgamma; }, bx * 64, p.d);
 }
 
-// ONE launch for both parts: workgroups [0, dx_blocks) compute dx rows, the rest the dgamma/dbeta column chunks.
-// They read the same x / dy at the same time (the second reader hits L2) and a kernel boundary disappears.
-// NCH = 0 selects the generic-d row kernel.
+// ONE launch for all parts: workgroups [0, dx_blocks) compute dx rows, [dx_blocks, cs_start) the dgamma/dbeta column
+// chunks, [cs_start, ...) the grouped column sums (bias gradients of the same block; none: cs_start = the grid).  They
+// read the same x / dy at the same time (the second reader hits L2) and kernel boundaries disappear.
 template <typename T, int NCH>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdMulti mj, const LnBwdMulti mp, int dx_blocks) {
-    if ((int)blockIdx.x < dx_blocks) {
-        if constexpr (NCH > 0) ln_bwd_dx_fast_body<T, NCH>(mj, blockIdx.x);
-        else ln_bwd_dx_body<T>(mj, blockIdx.x);
-    } else {
-        ln_bwd_param_body<T>(mp, blockIdx.x - dx_blocks);
-    }
+    if ((int)blockIdx.x < dx_blocks) ln_bwd_dx_body<T, NCH>(mj, blockIdx.x);
+    else ln_bwd_param_body<T>(mp, blockIdx.x - dx_blocks);
 }
-
-// ------------------------------------------------------------------------------------------------
-// column sums: out[n] += sum_m X[m,n]
-// ------------------------------------------------------------------------------------------------
-// Workgroup = 64 columns x `rows_per_block` rows: thread (cg = tid&15, rl = tid>>4) sums rows
-// rl, rl+16, ... of its 4 columns (16 threads x 8/16 B = one 128/256-B segment per row), the 16
-// row-lanes are reduced through LDS and ONE atomic per column leaves the workgroup, so at most
-// M/rows_per_block adders meet on an address (float atomics collapse under contention).
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_kernel(const T* X, int M, int N, int ldx, float* out, int rows_per_block) {
-    __shared__ float red[16][64 + 4];
-    const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int n = blockIdx.x * 64 + cg * 4;
-    const int m0 = blockIdx.y * rows_per_block, m1 = min(M, m0 + rows_per_block);
-    f32x4 acc = {0, 0, 0, 0};
-    if (n < N)
-#pragma unroll 8
-        for (int m = m0 + rl; m < m1; m += 16) acc += load4<T>(X + (size_t)m * ldx + n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[rl][cg * 4 + j] = acc[j];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += red[r][threadIdx.x];
-        const int col = blockIdx.x * 64 + threadIdx.x;
-        if (col < N) atomicAdd(out + col, t);
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void colsum_grouped_body(const GroupedColsum& c, int bid) {
-    __shared__ float red[16][64 + 4];
-    int g = 0;
-#pragma unroll
-    for (int i = 1; i < MEBT_MAX_GROUP; ++i)
-        if (i < c.n && bid >= c.blk_start[i]) g = i;
-    const GroupedColsum::Item& it = c.g[g];
-    const int b = bid - c.blk_start[g];
-    const int bx = b % it.gx, by = b / it.gx;
-    const T* X = reinterpret_cast<const T*>(it.X);
-    const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const int n = bx * 64 + cg * 4;
-    const int m0 = by * it.rpb, m1 = min(it.M, m0 + it.rpb);
-    f32x4 acc = {0, 0, 0, 0};
-    if (n < it.N)
-#pragma unroll 8
-        for (int m = m0 + rl; m < m1; m += 16) acc += load4<T>(X + (size_t)m * it.ldx + n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[rl][cg * 4 + j] = acc[j];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += red[r][threadIdx.x];
-        const int col = bx * 64 + threadIdx.x;
-        if (col < it.N) atomicAdd(it.out + col, t);
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_grouped_kernel(const GroupedColsum c) { colsum_grouped_body<T>(c, blockIdx.x); }
-
-// LayerNorm backward + the bias column sums of the same block in ONE launch: workgroups [0, dx_blocks) dx rows,
-// [dx_blocks, cs_start) dgamma/dbeta column chunks, [cs_start, ...) grouped column sums (ln_bwd_kernel above is the
-// two-part form; the body functions are shared)
 template <typename T, int NCH>
 __global__ __launch_bounds__(256) void ln_bwd_colsum_kernel(const LnBwdMulti mj, const LnBwdMulti mp, const GroupedColsum cs, int dx_blocks, int cs_start) {
-    if ((int)blockIdx.x < dx_blocks) {
-        if constexpr (NCH > 0) ln_bwd_dx_fast_body<T, NCH>(mj, blockIdx.x);
-        else ln_bwd_dx_body<T>(mj, blockIdx.x);
-    } else if ((int)blockIdx.x < cs_start) {
-        ln_bwd_param_body<T>(mp, blockIdx.x - dx_blocks);
-    } else {
-        colsum_grouped_body<T>(cs, blockIdx.x - cs_start);
-    }
+    if ((int)blockIdx.x < dx_blocks) ln_bwd_dx_body<T, NCH>(mj, blockIdx.x);
+    else if ((int)blockIdx.x < cs_start) ln_bwd_param_body<T>(mp, blockIdx.x - dx_blocks);
+    else colsum_grouped_body<T>(cs, blockIdx.x - cs_start);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -536,6 +438,38 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
+// The expressions of the loss kernels, per 4 logits at elements e .. e + 3 of a row.  ce_fwd + ce_bwd and ce_fused walk the
+// row in the same per-thread order through these, so both paths give the same statistics and gradient.
+// (1) running max, plain sum (label smoothing) and the number of logits that beat the target's (lt; ties: the lower index wins)
+__device__ __forceinline__ void ce_stats4(const f32x4& v, int e, float lt, long tgt, float& mx, float& sum, int& rank) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        mx = fmaxf(mx, v[q]);
+        sum += v[q];
+        rank += (v[q] > lt) || (v[q] == lt && (e + q) < tgt);
+    }
+}
+// (2) se += sum exp(v - max)
+__device__ __forceinline__ float ce_expsum4(const f32x4& v, float mx, float se) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) se += __expf(v[q] - mx);
+    return se;
+}
+// (3) the row's statistics from the block-wide sums (one thread stores them)
+__device__ __forceinline__ void ce_store_row(const CeParams& p, int row, float lse, float lt, float sum, float rk) {
+    const float eps = p.label_smoothing;
+    p.row_lse[row] = lse;
+    p.row_loss[row] = (1.f - eps) * (lse - lt) + eps * (lse - sum / p.V);
+    p.row_rank[row] = (int)(rk + 0.5f);
+}
+// (4) gradient (softmax - smoothed one-hot) * sc, with u = eps / V
+__device__ __forceinline__ f32x4 ce_grad4(const f32x4& v, int e, long tgt, float lse, float eps, float u, float sc) {
+    f32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = (__expf(v[q] - lse) - ((e + q) == tgt ? 1.f - eps : 0.f) - u) * sc;
+    return o;
+}
+
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const CeParams p) {
     __shared__ float sh[4];
     const int row = blockIdx.x;
@@ -548,36 +482,24 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const CeParams p) {
     int rank = 0;
     for (int e = threadIdx.x * 4; e < p.V; e += 1024) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(l + e);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mx = fmaxf(mx, v[q]);
-            sum += v[q];
-            rank += (v[q] > lt) || (v[q] == lt && (e + q) < tgt);
-        }
+        ce_stats4(v, e, lt, tgt, mx, sum, rank);
     }
     mx = block_max(mx, sh);
     float se = 0.f;
     for (int e = threadIdx.x * 4; e < p.V; e += 1024) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(l + e);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) se += __expf(v[q] - mx);
+        se = ce_expsum4(v, mx, se);
     }
     se = block_sum(se, sh);
     sum = block_sum(sum, sh);
     const float rk = block_sum((float)rank, sh);
-    if (threadIdx.x == 0) {
-        const float lse = mx + logf(se);
-        const float eps = p.label_smoothing;
-        p.row_lse[row] = lse;
-        p.row_loss[row] = (1.f - eps) * (lse - lt) + eps * (lse - sum / p.V);
-        p.row_rank[row] = (int)(rk + 0.5f);
-    }
+    if (threadIdx.x == 0) ce_store_row(p, row, mx + logf(se), lt, sum, rk);
 }
 
 // The same loss statistics AND the gradient of (loss_sum * scale) with respect to the logits from ONE pass over the row: the
 // 16384 logits of a row stay in registers (16 float4 per thread), so the row is read from HBM once instead of three times
-// (ce_fwd twice — the second time from L2 —, ce_bwd once).  Same per-thread summation order and the same expressions as
-// ce_fwd_kernel / ce_bwd_kernel: statistics and gradient agree with the two-kernel path to fp32 rounding.
+// (ce_fwd twice — the second time from L2 —, ce_bwd once).  Same per-thread summation order as ce_fwd_kernel / ce_bwd_kernel
+// and the shared expressions above: statistics and gradient agree with the two-kernel path to fp32 rounding.
 template <typename T, int NCH>
 __global__ __launch_bounds__(256) void ce_fused_kernel(const CeParams p) {
     __shared__ float sh[4];
@@ -595,38 +517,24 @@ __global__ __launch_bounds__(256) void ce_fused_kernel(const CeParams p) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int e = threadIdx.x * 4 + 1024 * c;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mx = fmaxf(mx, v[c][q]);
-            sum += v[c][q];
-            rank += (v[c][q] > lt) || (v[c][q] == lt && (e + q) < tgt);
-        }
+        ce_stats4(v[c], e, lt, tgt, mx, sum, rank);
     }
     mx = block_max(mx, sh);
     float se = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) se += __expf(v[c][q] - mx);
+    for (int c = 0; c < NCH; ++c) se = ce_expsum4(v[c], mx, se);
     se = block_sum(se, sh);
     sum = block_sum(sum, sh);
     const float rk = block_sum((float)rank, sh);
     const float lse = mx + logf(se);
     const float eps = p.label_smoothing;
-    if (threadIdx.x == 0) {
-        p.row_lse[row] = lse;
-        p.row_loss[row] = (1.f - eps) * (lse - lt) + eps * (lse - sum / p.V);
-        p.row_rank[row] = (int)(rk + 0.5f);
-    }
+    if (threadIdx.x == 0) ce_store_row(p, row, lse, lt, sum, rk);
     T* d = reinterpret_cast<T*>(p.dlogits) + (size_t)row * p.V;
     const float sc = p.grad_scale, u = eps / p.V;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         const int e = threadIdx.x * 4 + 1024 * c;
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = (__expf(v[c][q] - lse) - ((e + q) == tgt ? 1.f - eps : 0.f) - u) * sc;
-        store4<T>(d + e, o);
+        store4<T>(d + e, ce_grad4(v[c], e, tgt, lse, eps, u, sc));
     }
 }
 
@@ -664,10 +572,7 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const CeBwdParams p) {
     const float eps = p.label_smoothing, u = eps / p.V;
     for (int e = threadIdx.x * 4; e < p.V; e += 1024) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(l + e);
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = (__expf(v[q] - lse) - ((e + q) == tgt ? 1.f - eps : 0.f) - u) * sc;
-        store4<T>(d + e, o);
+        store4<T>(d + e, ce_grad4(v, e, tgt, lse, eps, u, sc));
     }
 }
 
@@ -752,6 +657,51 @@ int launch_embed_bwd(const EmbedBwdParams& p, int dtype, hipStream_t stream) {
     return rc;
 }
 
+// The row widths with a fixed-chunk instantiation of the LayerNorm kernels (LnRow): d == NCH * 64 * LaneVec<T>::V.
+namespace {
+template <typename T_, int NCH_> struct LnForm { using T = T_; static constexpr int NCH = NCH_; };
+struct LnWidth { int dtype, d, nch; };
+constexpr LnWidth LN_WIDTHS[] = {{MEBT_BF16, 1024, 2}, {MEBT_BF16, 512, 1}, {MEBT_BF16, 2048, 4}, {MEBT_F32, 1024, 4}, {MEBT_F32, 256, 1}};
+constexpr int LN_NWIDTHS = sizeof(LN_WIDTHS) / sizeof(LN_WIDTHS[0]);
+constexpr bool ln_widths_consistent() {
+    for (const LnWidth& w : LN_WIDTHS)
+        if (w.nch < 1 || w.d != w.nch * 64 * (w.dtype == MEBT_BF16 ? LaneVec<bf16_t>::V : LaneVec<float>::V)) return false;
+    return true;
+}
+static_assert(ln_widths_consistent(), "LN_WIDTHS: d must be NCH * 64 * (16 bytes of T)");
+
+// NCH of a launch whose jobs all have width d0 (same_d), 0 = the generic-d form
+int ln_nch(int dtype, bool same_d, int d0) {
+    for (const LnWidth& w : LN_WIDTHS)
+        if (same_d && w.dtype == dtype && w.d == d0) return w.nch;
+    return 0;
+}
+// f(LnForm<T, NCH>{}) for the (dtype, nch) that ln_nch gave
+template <int I = 0, typename F> void ln_dispatch(int dtype, int nch, F&& f) {
+    if constexpr (I == LN_NWIDTHS) {
+        if (dtype == MEBT_BF16) f(LnForm<bf16_t, 0>{});
+        else f(LnForm<float, 0>{});
+    } else {
+        if (LN_WIDTHS[I].dtype == dtype && LN_WIDTHS[I].nch == nch) f(LnForm<std::conditional_t<LN_WIDTHS[I].dtype == MEBT_BF16, bf16_t, float>, LN_WIDTHS[I].nch>{});
+        else ln_dispatch<I + 1>(dtype, nch, f);
+    }
+}
+template <typename P> int ln_jobs_nch(const P* j, int k, int dtype) {
+    bool same_d = true;
+    for (int i = 1; i < k; ++i) same_d = same_d && j[i].d == j[0].d;
+    return ln_nch(dtype, same_d, j[0].d);
+}
+
+// Rows per workgroup of a column sum over M rows and gx groups of 64 columns: <= 32 adders per address, but at least `fill`
+// workgroups (fill the chip) while a workgroup keeps 64 rows or more
+int colsum_rows_per_block(int M, int gx, int fill) {
+    int rpb = 256;
+    while ((M + rpb - 1) / rpb > 32) rpb *= 2;
+    while (rpb > 64 && (long)gx * ((M + rpb - 1) / rpb) < fill) rpb /= 2;
+    return rpb;
+}
+}  // namespace
+
 int launch_ln_fwd_multi(const LnFwdParams* jobs, int n, int dtype, hipStream_t stream) {
     LnFwdMulti mj;
     int k = 0, blocks = 0;
@@ -768,19 +718,10 @@ int launch_ln_fwd_multi(const LnFwdParams* jobs, int n, int dtype, hipStream_t s
     if (!k) return MEBT_OK;
     mj.n = k;
     for (int i = k; i <= MEBT_LN_MAXJ; ++i) mj.blk_start[i] = blocks;
-    bool same_d = true;
-    for (int i = 1; i < k; ++i) same_d = same_d && mj.j[i].d == mj.j[0].d;
-    const int d0 = mj.j[0].d;
-    if (dtype == MEBT_BF16) {
-        if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_fwd_fast_kernel<bf16_t, 2>), dim3(blocks), dim3(256), 0, stream, mj);
-        else if (same_d && d0 == 512) hipLaunchKernelGGL((ln_fwd_fast_kernel<bf16_t, 1>), dim3(blocks), dim3(256), 0, stream, mj);
-        else if (same_d && d0 == 2048) hipLaunchKernelGGL((ln_fwd_fast_kernel<bf16_t, 4>), dim3(blocks), dim3(256), 0, stream, mj);
-        else hipLaunchKernelGGL(ln_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, mj);
-    } else {
-        if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_fwd_fast_kernel<float, 4>), dim3(blocks), dim3(256), 0, stream, mj);
-        else if (same_d && d0 == 256) hipLaunchKernelGGL((ln_fwd_fast_kernel<float, 1>), dim3(blocks), dim3(256), 0, stream, mj);
-        else hipLaunchKernelGGL(ln_fwd_kernel<float>, dim3(blocks), dim3(256), 0, stream, mj);
-    }
+    ln_dispatch(dtype, ln_jobs_nch(mj.j, k, dtype), [&](auto form) {
+        using F = decltype(form);
+        hipLaunchKernelGGL((ln_fwd_kernel<typename F::T, F::NCH>), dim3(blocks), dim3(256), 0, stream, mj);
+    });
     CHECK_LAUNCH();
     return MEBT_OK;
 }
@@ -788,7 +729,7 @@ int launch_ln_fwd_multi(const LnFwdParams* jobs, int n, int dtype, hipStream_t s
 int launch_ln_fwd(const LnFwdParams& p, int dtype, hipStream_t stream) { return launch_ln_fwd_multi(&p, 1, dtype, stream); }
 
 static int prepare_colsum(const GroupedColsum& c, GroupedColsum& k, int& blocks_out);
-int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t stream, hipStream_t param_stream, const GroupedColsum* colsums) {
+int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t stream, const GroupedColsum* colsums) {
     LnBwdMulti mj, mp;
     int k = 0, blocks = 0, pblocks = 0;
     for (int i = 0; i < n; ++i) {
@@ -801,9 +742,7 @@ int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t s
         mj.blk_start[k] = blocks;
         blocks += (p.rows + 3) / 4;
         const int gx = (p.d + 63) / 64;
-        int rpb = 256;
-        while ((p.rows + rpb - 1) / rpb > 32) rpb *= 2;                                   // <= 32 adders per address
-        while (rpb > 64 && (long)gx * ((p.rows + rpb - 1) / rpb) < 256) rpb /= 2;         // but fill the chip
+        const int rpb = colsum_rows_per_block(p.rows, gx, 256);
         mp.rpw[k] = rpb;
         mp.blk_start[k] = pblocks;
         pblocks += gx * ((p.rows + rpb - 1) / rpb);
@@ -812,53 +751,27 @@ int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t s
     if (!k) return MEBT_OK;
     mj.n = mp.n = k;
     for (int i = k; i <= MEBT_LN_MAXJ; ++i) { mj.blk_start[i] = blocks; mp.blk_start[i] = pblocks; }
-    (void)param_stream;                      // all parts are one launch on `stream` now
-    bool same_d = true;
-    for (int i = 1; i < k; ++i) same_d = same_d && mj.j[i].d == mj.j[0].d;
-    const int d0 = mj.j[0].d;
     GroupedColsum cs;
     int cblocks = 0;
     if (colsums) { if (int rc = prepare_colsum(*colsums, cs, cblocks)) return rc; }
-    if (cblocks) {
-        const dim3 grid(blocks + pblocks + cblocks);
-        const int cs_start = blocks + pblocks;
-        if (dtype == MEBT_BF16) {
-            if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_bwd_colsum_kernel<bf16_t, 2>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-            else if (same_d && d0 == 512) hipLaunchKernelGGL((ln_bwd_colsum_kernel<bf16_t, 1>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-            else if (same_d && d0 == 2048) hipLaunchKernelGGL((ln_bwd_colsum_kernel<bf16_t, 4>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-            else hipLaunchKernelGGL((ln_bwd_colsum_kernel<bf16_t, 0>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-        } else {
-            if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_bwd_colsum_kernel<float, 4>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-            else if (same_d && d0 == 256) hipLaunchKernelGGL((ln_bwd_colsum_kernel<float, 1>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-            else hipLaunchKernelGGL((ln_bwd_colsum_kernel<float, 0>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
-        }
-        CHECK_LAUNCH();
-        return MEBT_OK;
-    }
-    const dim3 grid(blocks + pblocks);
-    if (dtype == MEBT_BF16) {
-        if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 2>), grid, dim3(256), 0, stream, mj, mp, blocks);
-        else if (same_d && d0 == 512) hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 1>), grid, dim3(256), 0, stream, mj, mp, blocks);
-        else if (same_d && d0 == 2048) hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 4>), grid, dim3(256), 0, stream, mj, mp, blocks);
-        else hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, 0>), grid, dim3(256), 0, stream, mj, mp, blocks);
-    } else {
-        if (same_d && d0 == 1024) hipLaunchKernelGGL((ln_bwd_kernel<float, 4>), grid, dim3(256), 0, stream, mj, mp, blocks);
-        else if (same_d && d0 == 256) hipLaunchKernelGGL((ln_bwd_kernel<float, 1>), grid, dim3(256), 0, stream, mj, mp, blocks);
-        else hipLaunchKernelGGL((ln_bwd_kernel<float, 0>), grid, dim3(256), 0, stream, mj, mp, blocks);
-    }
+    const int cs_start = blocks + pblocks;
+    const dim3 grid(cs_start + cblocks);
+    ln_dispatch(dtype, ln_jobs_nch(mj.j, k, dtype), [&](auto form) {
+        using F = decltype(form);
+        if (cblocks) hipLaunchKernelGGL((ln_bwd_colsum_kernel<typename F::T, F::NCH>), grid, dim3(256), 0, stream, mj, mp, cs, blocks, cs_start);
+        else hipLaunchKernelGGL((ln_bwd_kernel<typename F::T, F::NCH>), grid, dim3(256), 0, stream, mj, mp, blocks);
+    });
     CHECK_LAUNCH();
     return MEBT_OK;
 }
 
-int launch_ln_bwd(const LnBwdParams& p, int dtype, hipStream_t stream, hipStream_t param_stream) { return launch_ln_bwd_multi(&p, 1, dtype, stream, param_stream, nullptr); }
+int launch_ln_bwd(const LnBwdParams& p, int dtype, hipStream_t stream) { return launch_ln_bwd_multi(&p, 1, dtype, stream, nullptr); }
 
 int launch_colsum(const void* X, int M, int N, int ldx, float* out, int dtype, hipStream_t stream) {
     if (M <= 0 || N <= 0) return MEBT_OK;
     if (N % 4) { mebt_set_error("colsum: N must be a multiple of 4"); return MEBT_ESHAPE; }
     const int gx = (N + 63) / 64;
-    int rpb = 256;
-    while ((M + rpb - 1) / rpb > 32) rpb *= 2;          // <= 32 adders per address
-    while (rpb > 64 && (long)gx * ((M + rpb - 1) / rpb) < 256) rpb /= 2;   // but fill the chip
+    const int rpb = colsum_rows_per_block(M, gx, 256);
     const dim3 grid(gx, (M + rpb - 1) / rpb);
     if (dtype == MEBT_BF16) hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, stream, reinterpret_cast<const bf16_t*>(X), M, N, ldx, out, rpb);
     else hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, reinterpret_cast<const float*>(X), M, N, ldx, out, rpb);
@@ -873,10 +786,7 @@ static int prepare_colsum(const GroupedColsum& c, GroupedColsum& k, int& blocks_
         if (c.g[i].N % 4) { mebt_set_error("colsum: N must be a multiple of 4"); return MEBT_ESHAPE; }
         k.g[n] = c.g[i];
         k.g[n].gx = (c.g[i].N + 63) / 64;
-        int rpb = 256;
-        while ((c.g[i].M + rpb - 1) / rpb > 32) rpb *= 2;
-        while (rpb > 64 && (long)k.g[n].gx * ((c.g[i].M + rpb - 1) / rpb) < 128) rpb /= 2;
-        k.g[n].rpb = rpb;
+        const int rpb = k.g[n].rpb = colsum_rows_per_block(c.g[i].M, k.g[n].gx, 128);     // half the floor of the stand-alone sums
         k.blk_start[n] = blocks;
         blocks += k.g[n].gx * ((c.g[i].M + rpb - 1) / rpb);
         ++n;
@@ -886,6 +796,7 @@ static int prepare_colsum(const GroupedColsum& c, GroupedColsum& k, int& blocks_
     blocks_out = blocks;
     return MEBT_OK;
 }
+
 
 int launch_colsum_grouped(GroupedColsum& c, int dtype, hipStream_t stream) {
     GroupedColsum k;

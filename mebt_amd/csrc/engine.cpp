@@ -1069,7 +1069,7 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
             dproj = sc.dx_m;
         }
         if (side) RC(fork_side(m, st));
-        RC(launch_ln_bwd(p, dt, st, sd));
+        RC(launch_ln_bwd(p, dt, st));
     }
     lv.wgrad(dproj, d, a.att, d, m->gW + o.wp, d, d, Mq, m->gP + o.bp, bg);
     RC(dgrad(m, dproj, d, o.wp, x.datt, Mq, d, d, EPI_NONE, nullptr, 0, st, o.wq, 3 * dd));
@@ -1132,7 +1132,7 @@ static int backward_layer(mebt_model* m, int i, hipStream_t st) {
             x.doutm_ready = i - 1;
         }
     }
-    RC(launch_ln_bwd_multi(lj, nj, dt, st, sd, &lv.c));
+    RC(launch_ln_bwd_multi(lj, nj, dt, st, &lv.c));
     if (side) MEBT_HIP_CHECK(hipEventRecord(m->ev_layer[i & 1], sd));   // this scratch set is free once the side stream gets here
     return MEBT_OK;
 }

@@ -138,6 +138,8 @@ int launch_ln_fwd(const LnFwdParams& p, int dtype, hipStream_t stream);
 // several LayerNorms in ONE launch (the query and key sides of a block share LN1: gpt.py:180-181)
 constexpr int MEBT_LN_MAXJ = 3;
 int launch_ln_fwd_multi(const LnFwdParams* jobs, int n, int dtype, hipStream_t stream);
+// dx = LN'(dy + dy2) + (dx_add + old dx): the optional addends are summed first (old dx only with dx_accumulate), then added
+// to the LayerNorm gradient in one rounding step, at every width
 struct LnBwdParams {
     const void* x;                // LN input rows [rows,d] T
     const void* dy;               // grad wrt LN output, rows mapped like LnFwdParams (seg..)
@@ -150,11 +152,11 @@ struct LnBwdParams {
     void* dx2 = nullptr;          // optional second output: dx * dropout mask `drop2` (element index row*d + e), type of dx
     DropCfg drop2 = {0, 0, 0, 1.0f};
 };
-// dx rows and the dgamma/dbeta column reduction of `n` jobs in ONE launch on `stream` (param_stream is ignored: kept for callers)
-int launch_ln_bwd(const LnBwdParams& p, int dtype, hipStream_t stream, hipStream_t param_stream = nullptr);
+// dx rows and the dgamma/dbeta column reduction of `n` jobs in ONE launch on `stream`
+int launch_ln_bwd(const LnBwdParams& p, int dtype, hipStream_t stream);
 struct GroupedColsum;
 // `colsums` (optional): grouped column sums (bias gradients) executed by extra workgroups of the same launch
-int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t stream, hipStream_t param_stream = nullptr, const GroupedColsum* colsums = nullptr);
+int launch_ln_bwd_multi(const LnBwdParams* jobs, int n, int dtype, hipStream_t stream, const GroupedColsum* colsums = nullptr);
 
 // dst[i] = src[i] * keep(site, i)  (dropout mask re-applied in backward); TS/TD chosen by flags
 int launch_apply_dropout(const void* src, void* dst, size_t n, int src_f32, int dst_f32, const DropCfg& d, hipStream_t stream);

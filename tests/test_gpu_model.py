@@ -130,9 +130,11 @@ def test_train_steps_vs_golden(name):
         np.testing.assert_allclose(pn, g[f"s{s}_pnorm"], rtol=2e-5)
 
 
-@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+# width 64 runs the generic-d LayerNorm kernels; 256 (f32) and 512 (bf16) are the narrowest widths with a fixed-chunk instantiation
+@pytest.mark.parametrize("dtype,n_embd,n_head", [pytest.param("f32", 64, 2, id="f32"), pytest.param("bf16", 64, 2, id="bf16"),
+                                                 pytest.param("f32", 256, 4, id="f32-d256"), pytest.param("bf16", 512, 8, id="bf16-d512")])
 @pytest.mark.parametrize("drop", [0.0, 0.2])
-def test_maskgit_blocks_rewrite_both_streams(dtype, drop):
+def test_maskgit_blocks_rewrite_both_streams(dtype, n_embd, n_head, drop):
     """'maskgit' blocks (the padding mode of reference gpt.py:176-178,191-192,208-209) in the MIDDLE of a network:
     they rewrite contexts and targets, so later latent_enc blocks read the rewritten contexts and the gradient of the
     contexts stream is accumulated / handed back across them.  Forward, eval forward and every gradient vs the oracle
@@ -140,7 +142,7 @@ def test_maskgit_blocks_rewrite_both_streams(dtype, drop):
     from mebt_amd import _lib
     from mebt_amd.engine import NativeModel
     modes = ["latent_enc", "maskgit", "latent_self", "latent_enc", "latent_dec", "lt2l", "maskgit", "latent_enc", "latent_dec", "maskgit"]
-    cfg = orc.OracleConfig(len(modes), 2, 64, 32, 8, modes, shape=[2, 4, 4], budget=32, avg_loss=1.0)
+    cfg = orc.OracleConfig(len(modes), n_head, n_embd, 32, 8, modes, shape=[2, 4, 4], budget=32, avg_loss=1.0)
     nm = NativeModel(cfg.n_layer, cfg.n_head, cfg.n_embd, cfg.vocab_size, cfg.sos_emb, cfg.block_size, cfg.mode, dtype=dtype,
                      embd_pdrop=drop, resid_pdrop=drop, attn_pdrop=drop)
     nm.allocate(DEV)
@@ -179,7 +181,9 @@ def test_maskgit_blocks_rewrite_both_streams(dtype, drop):
         nm.backward(lg, scale)
         torch.cuda.synchronize()
         gv = nm.views(orc.param_shapes(cfg), grads=True)
-        lim = 2e-3 if dtype == "f32" else 1.2e-1
+        # bf16 at d = 512: the build before the row kernels were consolidated measured up to 0.175 here (eight runs: 0.12 .. 0.175, always
+        # a key bias of a block over the contexts, whose true gradient is zero but for rounding); the limit is twice that, like BF16_TOL
+        lim = 2e-3 if dtype == "f32" else 3.5e-1 if n_embd == 512 else 1.2e-1
         bad = []
         for k, p in P.items():
             ref = p.grad if p.grad is not None else torch.zeros_like(p)

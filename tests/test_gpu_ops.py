@@ -496,7 +496,9 @@ def test_gemm_strided_operands_exact_integers(dtype, a_kc, b_kc):
 
 
 @pytest.mark.parametrize("dtype,tol", [(_lib.BF16, 2e-2), (_lib.F32, 1e-5)])
-@pytest.mark.parametrize("rows,d", [(37, 64), (130, 256), (64, 1024), (5, 320)])
+# (9, 512) and (6, 2048): the other two fixed-chunk bf16 widths, the last workgroup with idle waves; in f32 the generic-d kernels at a
+# mid width and at their upper bound (all 8 chunks live)
+@pytest.mark.parametrize("rows,d", [(37, 64), (130, 256), (64, 1024), (5, 320), (9, 512), (6, 2048)])
 def test_layernorm_fwd_bwd(dtype, tol, rows, d):
     t = tdt(dtype)
     x = q(rnd(rows, d, seed=1) * 2 + 0.3, dtype)
