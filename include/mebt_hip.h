@@ -430,6 +430,33 @@ int mebt_op_i3d_maxpool(int32_t dtype, const void* in, void* out, int32_t B, int
  * the logits 1x1x1 convolution (w fp32 [ncls][C], bias fp32 [ncls] or NULL), the mean over time into logits [B, ncls]. */
 int mebt_op_i3d_head(int32_t dtype, const void* x, const float* w, const float* bias, float* pooled, float* logits, int32_t B, int32_t T,
                      int32_t H, int32_t W, int32_t C, int32_t ncls, mebt_stream_t stream);
+/* ---- LPIPS: the VGG-16 perceptual distance of the first stage (reference mebt/modules/lpips.py; VQGAN.validation_step's
+ * val/perceptual_loss, mebt/vqgan.py:104-107,190-196) ---------------------------------------------------------------------------------
+ * Activations are channels-last [N, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode); accumulation is
+ * fp32 in both.  All offsets are 64-bit; every entry checks its arguments before it launches and allocates nothing. */
+/* ScalingLayer on chosen frames: video fp32 [B, 3, T, H, W] (the VQGAN boundary tensor), frames int32 [n_frames][2] = (b, t) on the
+ * device -> out [n_frames, H, W, 3] = (x - shift[c]) / scale[c]: the subtraction, then the division, each rounded in fp32, then one
+ * rounding to `dtype`.  shift, scale: three floats each in HOST memory.  A (b, t) outside the video reads nothing and writes zeros. */
+int mebt_op_lpips_input(int32_t dtype, const float* video, const int32_t* frames, void* out, int32_t B, int32_t T, int32_t H, int32_t W,
+                        int64_t n_frames, const float* shift, const float* scale, mebt_stream_t stream);
+/* 3x3 convolution, stride 1, zero padding 1, bias (fp32 [Cout] or NULL), ReLU when relu != 0.  in [N, H, W, Cin], out [N, H, W, Cout];
+ * w: [Cout rounded up to 64][Kpad] of `dtype`, K = 9 Cin as (tap, ci) with ci fastest, Kpad = K rounded up to 32, zeros in the padding:
+ * the tensor mebt_op_i3d_conv takes for k = (1, 3, 3).  Cin == 3, or Cin a multiple of 32 up to 512; any N, H, W >= 1; in, w and out
+ * 16-byte aligned.  A workgroup stages a patch of the map with its halo into LDS once per 32 input channels and serves the nine taps
+ * from it.  The accumulation order of an output depends on nothing but Cin: an image gives the same bits alone and in any batch. */
+int mebt_op_conv2d_3x3(int32_t dtype, const void* in, const void* w, const float* bias, void* out, int32_t N, int32_t H, int32_t W,
+                       int32_t Cin, int32_t Cout, int32_t relu, mebt_stream_t stream);
+/* nn.MaxPool2d(2, 2): in [N, H, W, C] -> out [N, H / 2, W / 2, C] (rounded down, no padding).  H or W < 2: MEBT_STATUS_ESHAPE. */
+int mebt_op_maxpool_2x2(int32_t dtype, const void* in, void* out, int32_t N, int32_t H, int32_t W, int32_t C, mebt_stream_t stream);
+#define MEBT_LPIPS_HEAD_ROWS 16         /* pixels per workgroup of the head */
+/* One slice's term: feats [2 N, P, C] (N real images, then their N reconstructions; P = H W pixels), w fp32 [C] the slice's `lin`
+ * weights.  v[n] = (1 / P) sum_p sum_c w[c] (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2, |f| the L2 norm over channels
+ * (normalize_tensor: the eps outside the root, so a zero vector contributes exactly 0); out[n] += v[n] (fp64: the caller zeroes it and
+ * the five slices accumulate); layer_out (may be NULL): layer_out[n * layer_stride] = v[n].  Norms and the sum over channels are fp32
+ * (at most ceil(C / 64) terms per lane), fp64 from there; one fp64 partial per workgroup, added in index order by a second kernel: no
+ * float atomics, the same bits on every run.  scratch: 8-byte aligned, 8 * N * ceil(P / MEBT_LPIPS_HEAD_ROWS) bytes. */
+int mebt_op_lpips_head(int32_t dtype, const void* feats, const float* w, double* out, double* layer_out, int64_t layer_stride, int64_t N,
+                       int64_t P, int32_t C, void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
 
 /* ---- instrumentation ----------------------------------------------------------------------------- */
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py roofline): enable, run,

@@ -93,6 +93,10 @@ PROTOTYPES = {
     "mebt_op_abs_diff_sum": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "mebt_op_clip_quality_u8": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mebt_op_code_stats": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_op_lpips_input": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, C.POINTER(c_f32), C.POINTER(c_f32), c_vp]),
+    "mebt_op_conv2d_3x3": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 6 + [c_vp]),
+    "mebt_op_maxpool_2x2": (c_i32, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mebt_op_lpips_head": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
     "mebt_debug_dropout_mask": (c_i32, [C.c_uint64, C.c_uint32, c_f32, c_i64, c_vp, c_vp]),
     "mebt_debug_clock_probe": (c_i32, [c_vp, C.c_uint64, c_vp]),
     "mebt_debug_side_stream": (None, [c_vp, c_i32]),

@@ -4,7 +4,10 @@
 
 Flags: the data flags of VideoData (as `mebt_amd.measure_fvd` takes them), `--vqgan_ckpt`, `--n_sample` (2048), `--train`,
 `--packed_path`, `--vqgan_dtype {f16,f32}`, `--seed`, `--out FILE.csv`, `--save_np FILE.npy` (the reconstructed uint8 clips
-[N, T, H, W, 3]) and `--compute_fvd` with the I3D flags of measure_fvd (`--i3d_ckpt --i3d_dtype --i3d_batch`).
+[N, T, H, W, 3]), `--compute_fvd` with the I3D flags of measure_fvd (`--i3d_ckpt --i3d_dtype --i3d_batch`), and `--lpips` with
+`--lpips_ckpt FILE` (default: the `perceptual_model.*` tensors inside `--vqgan_ckpt`), `--lpips_dtype {f16,f32}` and `--lpips_every K`
+(every K-th frame of a clip, default 1): the VGG-16 perceptual distance between the float clips and their reconstructions
+(mebt_amd/lpips.py), the mean over all scored frames.
 
 Real side: `--image_folder` with `--data_path` a frame folder (train.txt under `--train`, else test.txt) is read through
 `VideoData(..., raw=True)`: the workers only decode, crop / resize / normalisation run in the frame-ingest kernel; with
@@ -14,7 +17,8 @@ split that ends sooner ends the run there and the count is printed.  Every batch
 clip for the metrics on the device; the clips, their reconstructions and every sum stay in HBM (mebt_amd/recon.py), one row of scalars
 is read back at the end.
 
-Output: one CSV row (pandas' to_csv layout, `measure_fvd.write_csv`) with the columns of `recon.FIELDS` (+ rFVD, rKVD), also printed.
+Output: one CSV row (pandas' to_csv layout, `measure_fvd.write_csv`) with the columns of `recon.FIELDS` (+ LPIPS) (+ rFVD, rKVD), also
+printed.
 """
 import argparse
 import os
@@ -28,6 +32,9 @@ from .data import TokenData
 from .measure_fvd import add_scoring_args, frame_folder, write_csv
 
 
+LPIPS_DTYPE_DEFAULT = 'f16'
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="reconstruction quality of a 3D-VQGAN checkpoint: recon loss, commitment loss, perplexity, "
                                                  "PSNR, SSIM and (--compute_fvd) rFVD / rKVD")
@@ -38,6 +45,10 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=0, help='seeds the one pass over the split (shuffle and start frames)')
     parser.add_argument('--out', type=str, default='recon.csv', help='the CSV the row is written to')
     parser.add_argument('--save_np', type=str, default='', help='.npy for the reconstructed uint8 clips [N, T, H, W, 3]')
+    parser.add_argument('--lpips', action='store_true', help='add the LPIPS column (VGG-16 perceptual distance of the reconstructions)')
+    parser.add_argument('--lpips_ckpt', type=str, default='', help="a state dict with the LPIPS tensors; default: those inside --vqgan_ckpt")
+    parser.add_argument('--lpips_dtype', type=str, default=LPIPS_DTYPE_DEFAULT, choices=['f16', 'f32'])
+    parser.add_argument('--lpips_every', type=int, default=1, help='score every K-th frame of a clip')
     return add_scoring_args(parser)              # --train --packed_path --compute_fvd --i3d_ckpt --i3d_dtype --i3d_batch
 
 
@@ -88,6 +99,20 @@ def main(argv=None):
     vqgan = load_vqgan(args.vqgan_ckpt, device)
     vqgan.compute_dtype = args.vqgan_dtype
     print(f'VQGAN compute dtype: {args.vqgan_dtype}')
+    if args.lpips:
+        if args.lpips_every < 1:
+            raise SystemExit(f'--lpips_every {args.lpips_every}: expected a positive integer')
+        if args.lpips_ckpt:
+            from .lpips import read_file
+            try:
+                vqgan.lpips_weights = read_file(args.lpips_ckpt)
+            except (ValueError, OSError) as e:
+                raise SystemExit(f'--lpips_ckpt {args.lpips_ckpt}: {e}')
+        if vqgan.lpips_weights is None:
+            raise SystemExit(f'--lpips: {args.vqgan_ckpt} holds no perceptual_model.* tensors; name a state dict that has the 13 VGG-16 '
+                             'convolutions and the five lin layers with --lpips_ckpt')
+        vqgan.lpips_dtype = args.lpips_dtype
+        print(f'LPIPS compute dtype: {args.lpips_dtype}, every {args.lpips_every} frame(s)')
     i3d = None
     if args.compute_fvd:
         from .fvd import frechet_distance, get_fvd_logits, polynomial_mmd
@@ -100,7 +125,7 @@ def main(argv=None):
         left = args.n_sample - acc.n_clips
         if len(x) > left:
             x, u8 = x[:left].contiguous(), u8[:left].contiguous()
-        st = vqgan.reconstruct_stats(x, clip_u8=u8)
+        st = vqgan.reconstruct_stats(x, clip_u8=u8, lpips_every=args.lpips_every if args.lpips else 0)
         acc.add(st)
         if args.save_np:
             saved.append(st["recon_u8"])
@@ -114,7 +139,7 @@ def main(argv=None):
     if acc.n_clips < args.n_sample:
         print(f'the split ended after {acc.n_clips} clips, fewer than --n_sample {args.n_sample}')
     row = acc.result()
-    columns = list(recon.FIELDS)
+    columns = list(recon.FIELDS) + (["LPIPS"] if args.lpips else [])
     if i3d is not None:
         real, fake = torch.cat(emb_real, 0), torch.cat(emb_fake, 0)
         row["rFVD"], row["rKVD"] = float(frechet_distance(fake, real)), float(polynomial_mmd(fake, real))

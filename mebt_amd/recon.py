@@ -172,13 +172,15 @@ class ReconAccumulator:
     recon_loss / commitment_loss: the reference's figures over the whole set (equal to its per-batch values averaged with the batch
     sizes as weights); perplexity: the same average of the per-batch perplexities, which is what the reference logs; perplexity_set:
     the perplexity of the whole set's histogram; codes_used: the fraction of codes hit at least once; PSNR: the mean over frames
-    of 10 log10(255^2 / MSE), frames without any error left out and counted as identical_frames; SSIM: the mean over frames."""
+    of 10 log10(255^2 / MSE), frames without any error left out and counted as identical_frames; SSIM: the mean over frames.  When the
+    dicts carry `lpips` (reconstruct_stats(lpips_every=k)), `result()` ends with LPIPS: the mean over all scored frames."""
 
     def __init__(self, n_codes, l1_weight=4.0, device="cuda"):
         self.l1_weight = float(l1_weight)
         self.hist = torch.zeros(n_codes, device=device, dtype=torch.int64)
         self.sums = torch.zeros(6, device=device, dtype=torch.float64)    # |x - y|, |z - e|^2, B * perplexity, PSNR, SSIM, identical frames
-        self.n_clips = self.n_values = self.n_z = self.n_frames = 0
+        self.lpips_sum = torch.zeros((), device=device, dtype=torch.float64)
+        self.n_clips = self.n_values = self.n_z = self.n_frames = self.n_lpips = 0
 
     def add(self, st):
         B = int(st["abs_sum"].shape[0])
@@ -190,6 +192,9 @@ class ReconAccumulator:
         self.n_values += st["recon"].numel()
         self.n_z += st["z_values"]
         self.n_frames += st["sq_err"].numel()
+        if st.get("lpips") is not None:
+            self.lpips_sum += st["lpips"].double().sum()
+            self.n_lpips += st["lpips"].numel()
 
     def result(self):
         if self.n_clips == 0:
@@ -198,8 +203,11 @@ class ReconAccumulator:
         hist = self.hist.cpu()
         identical = int(round(s[5]))
         differing = self.n_frames - identical
-        return {"recon_loss": s[0] / self.n_values * self.l1_weight, "commitment_loss": 0.25 * s[1] / self.n_z,
-                "perplexity": s[2] / self.n_clips, "perplexity_set": float(perplexity_of(hist)),
-                "codes_used": float((hist > 0).sum()) / hist.numel(),
-                "PSNR": s[3] / differing if differing else math.inf, "SSIM": s[4] / self.n_frames,
-                "identical_frames": identical, "n_clips": self.n_clips}
+        res = {"recon_loss": s[0] / self.n_values * self.l1_weight, "commitment_loss": 0.25 * s[1] / self.n_z,
+               "perplexity": s[2] / self.n_clips, "perplexity_set": float(perplexity_of(hist)),
+               "codes_used": float((hist > 0).sum()) / hist.numel(),
+               "PSNR": s[3] / differing if differing else math.inf, "SSIM": s[4] / self.n_frames,
+               "identical_frames": identical, "n_clips": self.n_clips}
+        if self.n_lpips:
+            res["LPIPS"] = float(self.lpips_sum) / self.n_lpips
+        return res

@@ -2,9 +2,10 @@
 operators of csrc/vqgan.hip.  Same constructor argument (`args` namespace with n_hiddens / downsample / image_channels /
 embedding_dim / n_codes), module tree and state-dict names (`encoder.conv_first.conv.weight`, `encoder.conv_blocks.0.res.norm1.weight`,
 `decoder.conv_blocks.0.up.convt.weight`, `pre_vq_conv.conv.weight`, `codebook.embeddings`, ...) so reference checkpoints load;
-the discriminators / LPIPS / training losses (training of the first stage, SURVEY.md §2 OUT-OF-SCOPE) are not built and their keys are
-ignored on load.  `validation_step` (vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric
-operators of csrc/recon/recon.hip (mebt_amd/recon.py).
+the discriminators and the training losses (training of the first stage, SURVEY.md §2 OUT-OF-SCOPE) are not built and their keys are
+ignored on load; the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
+(vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric operators of csrc/recon/recon.hip
+(mebt_amd/recon.py) and, when the checkpoint carried the perceptual weights, csrc/lpips/lpips.hip.
 
 The nn.Modules below only HOLD parameters.  `encode` / `decode` walk a launch plan: every convolution is one
 `mebt_op_conv3d` call per output sub-lattice (1 for a convolution, 4 or 8 for a stride-2 transposed convolution), every
@@ -236,10 +237,42 @@ class VQGAN(nn.Module):
         return model
 
     def load_state_dict(self, state_dict, strict=True, **kw):
-        """discriminator / perceptual-loss tensors of a reference checkpoint are not part of the inference path"""
-        skip = ("image_discriminator.", "video_discriminator.", "perceptual_model.")
+        """The discriminators of a reference checkpoint are not part of the inference path and are skipped.  Its `perceptual_model.*`
+        tensors (the reference's LPIPS sub-module: 13 VGG-16 convolutions, five `lin` layers, two scaling buffers) are kept as CPU
+        tensors in the plain attribute `lpips_weights`, not as parameters or buffers: `state_dict()` and `.to()` do not see them.
+        A partial set raises, naming what is missing; a state dict without any leaves an earlier set in place."""
+        from . import lpips as _lpips
+        skip = ("image_discriminator.", "video_discriminator.", _lpips.PREFIX)
         sd = {k: v for k, v in state_dict.items() if not k.startswith(skip)}
+        if any(k.startswith(_lpips.PREFIX) for k in state_dict):
+            own = _lpips.extract({k: v for k, v in state_dict.items() if k.startswith(_lpips.PREFIX)})
+            if own is not None:
+                self.lpips_weights = own
         return super().load_state_dict(sd, strict=strict, **kw)
+
+    @property
+    def lpips_weights(self):
+        return self.__dict__.get("_lpips_weights")
+
+    @lpips_weights.setter
+    def lpips_weights(self, own):
+        self.__dict__["_lpips_weights"] = own
+        self.__dict__["_lpips_built"] = None
+
+    @property
+    def lpips(self):
+        """None without perceptual weights; else `mebt_amd.lpips.LPIPS` on the model's device, built at first use.  Its compute dtype is
+        `lpips_dtype` ("f16" / "f32"), or the model's `compute_dtype` while that is None."""
+        own = self.lpips_weights
+        if own is None:
+            return None
+        from .lpips import LPIPS
+        key = (self.__dict__.get("lpips_dtype") or self.compute_dtype, self.codebook.embeddings.device)
+        built = self.__dict__.get("_lpips_built")
+        if built is None or built[0] != key:
+            built = (key, LPIPS(own, dtype=key[0], device=key[1]))
+            self.__dict__["_lpips_built"] = built
+        return built[1]
 
     # ---- preparation ---------------------------------------------------------------------------------------------------
     def _prepare(self):
@@ -386,13 +419,14 @@ class VQGAN(nn.Module):
         self.__dict__.setdefault("logged", {})[name] = value
 
     @torch.no_grad()
-    def reconstruct_stats(self, x, clip_u8=None):
+    def reconstruct_stats(self, x, clip_u8=None, lpips_every=0):
         """x float32 [B, 3, T, H, W] on the GPU -> the reconstruction and the sums its quality figures are made of, all on the device:
         `recon` (decode(encode(x))), `ids`, `abs_sum` [B] = sum |recon - x|, `hist` [n_codes] of this batch's ids, `commit_sq_sum` [1] =
         sum |z - e|^2, `sq_err` / `ssim` [B, T] per frame of the byte clips `real_u8` / `recon_u8` [B, T, H, W, 3].  The bytes of both sides
         are `frames.video_to_clip_u8`'s, what the sampling scripts save and FVD reads; `clip_u8` hands in the real side's when the
         caller has them already (a raw batch's `to_clip_u8()`: the same bytes).  `frame_bytes` and `z_values` are the element counts
-        the means divide by."""
+        the means divide by.  `lpips_every` = k > 0 adds `lpips` float64 [B, ceil(T / k)]: LPIPS(x, recon) of frames 0, k, 2k, ... of every
+        clip on the float tensors (it needs the checkpoint's perceptual weights: `self.lpips`)."""
         from . import recon
         from .frames import video_to_clip_u8
         x = x.to(torch.float32).contiguous()
@@ -404,15 +438,29 @@ class VQGAN(nn.Module):
         real_u8 = video_to_clip_u8(x) if clip_u8 is None else clip_u8
         recon_u8 = video_to_clip_u8(rec)
         sq_err, ssim = recon.clip_quality_u8(real_u8, recon_u8)
-        return {"recon": rec, "ids": ids, "abs_sum": recon.abs_diff_sum(x.view(B, -1), rec.view(B, -1)), "hist": hist,
-                "commit_sq_sum": sq_sum, "sq_err": sq_err, "ssim": ssim, "real_u8": real_u8, "recon_u8": recon_u8,
-                "frame_bytes": int(np.prod(real_u8.shape[2:])), "z_values": z.numel()}
+        st = {"recon": rec, "ids": ids, "abs_sum": recon.abs_diff_sum(x.view(B, -1), rec.view(B, -1)), "hist": hist,
+              "commit_sq_sum": sq_sum, "sq_err": sq_err, "ssim": ssim, "real_u8": real_u8, "recon_u8": recon_u8,
+              "frame_bytes": int(np.prod(real_u8.shape[2:])), "z_values": z.numel()}
+        if lpips_every:
+            if lpips_every < 0:
+                raise ValueError(f"reconstruct_stats: lpips_every must be >= 0, got {lpips_every}")
+            net = self.lpips
+            if net is None:
+                raise RuntimeError("reconstruct_stats: lpips_every needs the perceptual weights (a checkpoint with perceptual_model.* tensors, "
+                                   "or `lpips_weights` set from mebt_amd.lpips.read_file)")
+            ts = list(range(0, x.shape[2], int(lpips_every)))
+            st["lpips"] = net(x, rec, frames=[(b, t) for b in range(B) for t in ts]).view(B, len(ts))
+        return st
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):
         """VQGAN.validation_step (vqgan.py:190-196): logs and returns val/recon_loss = mean |x_recon - x| * l1_weight, val/commitment_loss
-        = 0.25 * mean (z - e)^2 and val/perplexity of the batch (0-dim float64 tensors on the device).  The perceptual term needs LPIPS'
-        VGG weights, which are not built: it is logged as 0 when perceptual_weight is 0 (the reference's default) and left out otherwise."""
+        = 0.25 * mean (z - e)^2 and val/perplexity of the batch (0-dim float64 tensors on the device).  val/perceptual_loss: with
+        perceptual_weight 0 (the reference's default) it is 0 and nothing is drawn.  Otherwise, when the checkpoint carried the
+        perceptual weights (`self.lpips`), one frame per clip is drawn after the reconstruction as the reference draws it
+        (`torch.randint(0, T, [B])` on the default CPU generator, vqgan.py:104, its only random call on this path) and the value is
+        mean_b LPIPS(x[b, :, idx_b], recon[b, :, idx_b]) * perceptual_weight.  The reference would hand Lightning the [B, 1, 1, 1] tensor,
+        which it accepts at B = 1 only; the mean equals it there.  Without the weights the term is left out, with a notice."""
         from . import recon
         from .frames import to_device_video
         x = to_device_video(batch["video"], self.codebook.embeddings.device)
@@ -420,8 +468,12 @@ class VQGAN(nn.Module):
         out = {"val/recon_loss": st["abs_sum"].sum() / st["recon"].numel() * float(self._hp("l1_weight", 4.0)),
                "val/commitment_loss": 0.25 * st["commit_sq_sum"][0] / st["z_values"],
                "val/perplexity": recon.perplexity_of(st["hist"])}
-        if float(self._hp("perceptual_weight", 0.0)) == 0.0:
+        pw = float(self._hp("perceptual_weight", 0.0))
+        if pw == 0.0:
             out["val/perceptual_loss"] = torch.zeros((), device=x.device, dtype=torch.float64)
+        elif self.lpips is not None:
+            frame_idx = torch.randint(0, x.shape[2], [x.shape[0]])
+            out["val/perceptual_loss"] = self.lpips(x, st["recon"], frames=frame_idx).mean() * pw
         else:
             print("validation_step: val/perceptual_loss is left out (LPIPS is not built)")
         for k, v in out.items():
