@@ -335,6 +335,46 @@ int mebt_op_embedding_rows(int32_t dtype, const int64_t* ids, const float* embed
 /* fp32 -> fp16 cast of a flat buffer (n multiple of 4). */
 int mebt_op_cast_f16(const float* src, void* dst, int64_t n, mebt_stream_t stream);
 
+/* ---- 3D-VQGAN first stage, backward (csrc/vqgan_bwd/vqgan_bwd.hip; reference mebt/vqgan.py:98-102,183-184 before discriminator_iter_start) -----
+ * Same conventions as above.  Every floating-point sum over workgroups is a fixed-order sum of fp32 partial slabs in caller-sized
+ * scratch (no float atomics, no hand-off inside a launch): the same inputs give the same bits.  `inv_scale` (1 / S of a backward pass
+ * seeded with the power-of-two gradient scale S) multiplies the parameter gradients in the fp32 epilogue.
+ *
+ * Data gradient of one mebt_conv3d_desc class: the gradient on the PADDED input lattice (q = clamp-free coordinate + front) is a
+ * convolution of dy that reads zeros outside dy; mebt_op_pad_zero makes the zero border physical so that mebt_op_conv3d computes it
+ * (out_mode 1, fp32), and mebt_op_halo_fold adds every lattice position onto the voxel the forward's clamp mapped it to.
+ * mebt_op_pad_zero: dst [B, pT, pH, pW, C] of `dtype`, channels-last = src placed at (fT, fH, fW), zero elsewhere; src [B, T, H, W, C]
+ * of `dtype` (src_mode 0) or fp32 (1), or fp32 [B, C, T, H, W] (2).  p >= n + f per dimension, else MEBT_STATUS_ESHAPE. */
+int mebt_op_pad_zero(int32_t dtype, const void* src, void* dst, int32_t B, int32_t T, int32_t H, int32_t W, int32_t fT, int32_t fH,
+                     int32_t fW, int32_t pT, int32_t pH, int32_t pW, int32_t C, int32_t src_mode, mebt_stream_t stream);
+/* dx[b, i, c] = add[b, i, c] + sum of dxp[b, q, c] over the lattice positions q (fp32 [B, pT, pH, pW, C]) with clamp(q - f, 0, n - 1) == i
+ * per dimension: q = i + f inside, the first voxel also takes q < f, the last one q >= n + f, a one-voxel axis all of them.  add
+ * (channels-last `dtype`, the residual branch's gradient) may be NULL.  dx: channels-last `dtype` (out_mode 0) or fp32 (1). */
+int mebt_op_halo_fold(int32_t dtype, const float* dxp, const void* add, void* dx, int32_t B, int32_t T, int32_t H, int32_t W, int32_t pT,
+                      int32_t pH, int32_t pW, int32_t fT, int32_t fH, int32_t fW, int32_t C, int32_t out_mode, mebt_stream_t stream);
+/* Weight and bias gradient of one class: dw[co][j][ci] = inv_scale * sum_o dy[o][co] x[clamp(o' sm + tap[j])][ci] (fp32, the class layout
+ * [Cout][ntaps][Cin]) and db[co] = inv_scale * sum_o dy[o][co] (NULL: not wanted).  The descriptor is the forward's: `in` = x (in_mode 0
+ * or 1), `out` = dy in the layout of out_mode (0, 1 or 2; read only), `w`, `bias`, `resid` unused.  fp16: v_mfma_f32_16x16x32_f16 on
+ * operands rounded to fp16; fp32: FMAs.  The voxels are split over at most `nsplit` workgroups per tile; scratch holds
+ * mebt_conv3d_wgrad_scratch_bytes(d, nsplit) bytes.  An empty class writes zeros. */
+int64_t mebt_conv3d_wgrad_scratch_bytes(const mebt_conv3d_desc* d, int32_t nsplit);
+int mebt_op_conv3d_wgrad(int32_t dtype, const mebt_conv3d_desc* d, float* dw, float* db, float inv_scale, int32_t nsplit, void* scratch,
+                         int64_t scratch_bytes, mebt_stream_t stream);
+/* Backward of y = silu(GroupNorm_32(x)): with xhat, h = xhat gamma + beta and s = sigmoid(h) recomputed from x and the forward's `stats`,
+ * dh = dy s (1 + h (1 - s)); dgamma_c = inv_scale * sum dh xhat, dbeta_c = inv_scale * sum dh; dx = rstd (gamma dh - mean_g(gamma dh) -
+ * xhat mean_g(gamma dh xhat)) + add (add: channels-last `dtype` or NULL).  x, dy, dx channels-last `dtype`.  scratch (8-byte aligned):
+ * mebt_groupnorm_silu_bwd_scratch_bytes(B, vox_per_sample, C) bytes. */
+int64_t mebt_groupnorm_silu_bwd_scratch_bytes(int32_t B, int64_t vox_per_sample, int32_t C);
+int mebt_op_groupnorm_silu_bwd(int32_t dtype, const void* x, const float* stats, const float* gamma, const float* beta, const void* dy,
+                               const void* add, void* dx, float* dgamma, float* dbeta, float inv_scale, int32_t B,
+                               int64_t vox_per_sample, int32_t C, void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+/* out[i] = c * sign(x_recon[i] - x[i]) with sign(0) = 0: the gradient of c * sum |x_recon - x| (c = S * l1_weight / n). */
+int mebt_op_l1_seed(const float* x_recon, const float* x, float* out, int64_t n, float c, mebt_stream_t stream);
+/* dz[m, :] = c * (z[m, :] - embeddings[ids[m], :]) + g_st[m, :]: the commitment term (c = S * 0.5 / numel(z)) plus the straight-through
+ * gradient arriving at the quantised embeddings (codebook.py:64,91); g_st may be NULL.  All fp32 [M, d]. */
+int mebt_op_vq_seed(const float* z, const float* embeddings, const int64_t* ids, const float* g_st, float* dz, int64_t M, int32_t d,
+                    int32_t n_codes, float c, mebt_stream_t stream);
+
 /* ---- frame ingest for pixel-space training (reference mebt/data.py FrameListDataset.getTensor) ------------------------------
  * Uint8 RGB frames [N, Hs, Ws, 3] (N = clips x T) -> crop [y0, y0 + S) x [x0, x0 + S) -> PIL Image.resize((R, R), BILINEAR) ->
  * float32(u) / 255 - 0.5 through `lut` [256] -> out [Bout, 3, T, R, R] fp32; clip i goes to slot slots[i] (NULL: slot i, a slot

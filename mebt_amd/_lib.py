@@ -81,6 +81,14 @@ PROTOTYPES = {
     "mebt_op_codebook_argmin_filtered": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_embedding_rows": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "mebt_op_cast_f16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
+    "mebt_op_pad_zero": (c_i32, [c_i32, c_vp, c_vp] + [c_i32] * 12 + [c_vp]),
+    "mebt_op_halo_fold": (c_i32, [c_i32, c_vp, c_vp, c_vp] + [c_i32] * 12 + [c_vp]),
+    "mebt_conv3d_wgrad_scratch_bytes": (c_i64, [c_vp, c_i32]),
+    "mebt_op_conv3d_wgrad": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_groupnorm_silu_bwd_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32]),
+    "mebt_op_groupnorm_silu_bwd": (c_i32, [c_i32] + [c_vp] * 9 + [c_f32, c_i32, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_op_l1_seed": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_vp]),
+    "mebt_op_vq_seed": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_f32, c_vp]),
     "mebt_op_i3d_preprocess": (c_i32, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_i3d_conv": (c_i32, [c_i32, c_vp, c_vp]),
     "mebt_op_i3d_maxpool": (c_i32, [c_i32, c_vp, c_vp] + [c_i32] * 11 + [c_vp]),

@@ -2,16 +2,20 @@
 operators of csrc/vqgan.hip.  Same constructor argument (`args` namespace with n_hiddens / downsample / image_channels /
 embedding_dim / n_codes), module tree and state-dict names (`encoder.conv_first.conv.weight`, `encoder.conv_blocks.0.res.norm1.weight`,
 `decoder.conv_blocks.0.up.convt.weight`, `pre_vq_conv.conv.weight`, `codebook.embeddings`, ...) so reference checkpoints load;
-the discriminators and the training losses (training of the first stage, SURVEY.md §2 OUT-OF-SCOPE) are not built and their keys are
-ignored on load; the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
+the discriminators, the EMA codebook update and the perceptual term's backward are not built (their keys are ignored on load): of
+first-stage training, `recon_backward` gives the gradients of recon_loss + commitment_loss (vqgan.py:98-102,183-184 before
+discriminator_iter_start, perceptual_weight 0) on the kernels of csrc/vqgan_bwd/vqgan_bwd.hip with the codebook frozen, and `configure_optimizers`
+the reference's autoencoder Adam; the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
 (vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric operators of csrc/recon/recon.hip
 (mebt_amd/recon.py) and, when the checkpoint carried the perceptual weights, csrc/lpips/lpips.hip.
 
-The nn.Modules below only HOLD parameters.  `encode` / `decode` walk a launch plan: every convolution is one
+The nn.Modules below only HOLD parameters (and, after `recon_backward`, their `.grad`); no autograd graph is ever built.  `encode` /
+`decode` walk a launch plan: every convolution is one
 `mebt_op_conv3d` call per output sub-lattice (1 for a convolution, 4 or 8 for a stride-2 transposed convolution), every
 Normalize + SiLU one `mebt_op_groupnorm_silu`, the codebook search one `mebt_op_codebook_argmin`.  Activations stay
 channels-last on the GPU; `compute_dtype` = "f16" (MFMA, BASELINE config 5) or "f32" (parity).  Weights are re-laid out
-([Cout][tap][Cin]) and cast once, at the first call after a (re)load.  No CPU / eager-torch compute path exists.
+([Cout][tap][Cin]) and cast once, at the first call after a (re)load or after an in-place parameter update (the parameters' version
+counters are part of the cache key, so an optimizer step is noticed).  No CPU / eager-torch compute path exists.
 """
 import ctypes as C
 import math
@@ -148,6 +152,8 @@ class _Conv:
         self.bias = bias.detach().to(dev, torch.float32).contiguous() if bias is not None else None
         self.transposed, self.kernel, self.stride = transposed, kernel, stride
         self.classes = []            # (pi, taps [n,3] int, weights [Cout, n, Cin])
+        self.sels = []               # transposed: per class, the (kt, kh, kw) of its taps in the nn.ConvTranspose3d weight
+        self._plans = {}             # input dims -> data-gradient plan
         w = weight.detach().to(torch.float32)
         if not transposed:
             self.cout, self.cin = w.shape[0], w.shape[1]
@@ -185,12 +191,77 @@ class _Conv:
                         idx = torch.tensor(sel, device=dev)
                         wc = w[:, :, idx[:, 0], idx[:, 1], idx[:, 2]]                                    # [Cin, Cout, n]
                         self.classes.append(((pt, ph, pw), taps, wc.permute(1, 2, 0).to(tdt).contiguous()))
+                        self.sels.append(sel)
             self.os, self.sm = stride, (1, 1, 1)
 
     def out_dims(self, dims):
         if self.transposed:
             return tuple(d * s for d, s in zip(dims, self.stride))
         return tuple(d // s for d, s in zip(dims, self.stride))
+
+    # ---- backward geometry (host side only: integers and weight re-layouts) -------------------------------------------------------
+    def class_counts(self, od, pi):
+        return [(o - p + s - 1) // s for o, p, s in zip(od, pi, self.os)]
+
+    def dgrad_plan(self, dims):
+        """The data gradient of this layer at input size `dims`, as convolutions of dy on the PADDED input lattice.  The forward reads,
+        for output voxel o = o' * os + pi and tap j, the input position p = o' * sm + tap[j] before the clamp; the lattice holds every such
+        p, q = p - lo per dimension (`front` = -lo, size `pd`).  dxp[q] = sum w[co][j][ci] dy[o] over the (o', j) with o' * sm + tap[j] == p,
+        dy read as ZERO outside its box: the caller copies dy into a zero box of size `zd` at offset `fz`, wide enough that no tap
+        leaves it.  A convolution (os = 1) gives one class per parity of q modulo sm (a transposed convolution of dy); a transposed
+        one (sm = 1) gives a single strided class over the taps of all its forward classes.  `classes`: dicts os / pi / sm / cq (class
+        counts) / taps (into the zero box) / w ([Cin][n][Cout], None for a parity no tap reaches)."""
+        import itertools
+        key = tuple(dims)
+        if key in self._plans:
+            return self._plans[key]
+        od = self.out_dims(dims)
+        taps_all = [t for _, taps, _ in self.classes for t in taps]
+        lo = [min(0, min(t[k] for t in taps_all)) for k in range(3)]
+        hi = [max(0, max(t[k] for t in taps_all)) for k in range(3)]
+        cmax = [max(self.class_counts(od, pi)[k] for pi, _, _ in self.classes) for k in range(3)]
+        pd = [max((cmax[k] - 1) * self.sm[k] + hi[k], dims[k] - 1) - lo[k] + 1 for k in range(3)]
+        gcls = []
+        if not self.transposed:
+            (_, taps, w), = self.classes
+            for r in itertools.product(*[range(s) for s in self.sm]):
+                sel, offs = [], []
+                for j, t in enumerate(taps):
+                    num = [r[k] + lo[k] - t[k] for k in range(3)]
+                    if all(n % s == 0 for n, s in zip(num, self.sm)):
+                        sel.append(j)
+                        offs.append(tuple(n // s for n, s in zip(num, self.sm)))
+                cq = [(pd[k] - r[k] + self.sm[k] - 1) // self.sm[k] for k in range(3)]
+                gcls.append(dict(os=tuple(self.sm), pi=r, sm=(1, 1, 1), cq=cq, offs=offs,
+                                 w=w[:, sel, :].permute(2, 1, 0).contiguous() if sel else None))
+        else:
+            offs, ws = [], []
+            for pi, taps, w in self.classes:
+                offs += [tuple((lo[k] - t[k]) * self.os[k] + pi[k] for k in range(3)) for t in taps]
+                ws.append(w)
+            gcls.append(dict(os=(1, 1, 1), pi=(0, 0, 0), sm=tuple(self.os), cq=list(pd), offs=offs,
+                             w=torch.cat(ws, dim=1).permute(2, 1, 0).contiguous()))
+        live = [c for c in gcls if c["offs"] and min(c["cq"]) > 0]
+        mn = [min([0] + [min(o[k] for o in c["offs"]) for c in live]) for k in range(3)]
+        mx = [max([od[k] - 1] + [(c["cq"][k] - 1) * c["sm"][k] + max(o[k] for o in c["offs"]) for c in live]) for k in range(3)]
+        fz = [-mn[k] for k in range(3)]
+        zd = [fz[k] + mx[k] + 1 for k in range(3)]
+        for c in gcls:
+            c["taps"] = [tuple(o[k] + fz[k] for k in range(3)) for o in c["offs"]]
+            assert len(c["taps"]) <= 64 and all(-128 <= v < 128 for t in c["taps"] for v in t), (self.kernel, self.stride)
+        plan = dict(front=[-v for v in lo], pd=pd, fz=fz, zd=zd, classes=gcls)
+        self._plans[key] = plan
+        return plan
+
+    def full_weight_grad(self, dws):
+        """per-class gradients [Cout][n][Cin] (fp32) -> the shape of the nn.Conv3d / nn.ConvTranspose3d weight"""
+        if not self.transposed:
+            return dws[0].view(self.cout, *self.kernel, self.cin).permute(0, 4, 1, 2, 3).contiguous()
+        g = torch.zeros(self.cin, self.cout, *self.kernel, device=dws[0].device, dtype=torch.float32)
+        for dw, sel in zip(dws, self.sels):
+            idx = torch.tensor(sel, device=dw.device)
+            g[:, :, idx[:, 0], idx[:, 1], idx[:, 2]] = dw.permute(2, 0, 1)
+        return g
 
 
 class _Desc(C.Structure):
@@ -219,6 +290,7 @@ class VQGAN(nn.Module):
         self.compute_dtype = "f16"
         self.use_mfma = True
         self._prepared = None
+        self._tape = None            # recon_backward's training forward: {layer -> what its backward reads}
         self.register_load_state_dict_post_hook(lambda module, incompatible: setattr(module, "_prepared", None))
 
     @property
@@ -279,7 +351,8 @@ class VQGAN(nn.Module):
         dev = self.codebook.embeddings.device
         if dev.type != "cuda":
             raise RuntimeError("mebt_amd.vqgan runs on MI355X only: move the model to the GPU (there is no CPU path in the product)")
-        key = (self.compute_dtype, dev)
+        # the parameters' version counters: an optimizer step (an in-place update) makes the re-laid-out weights stale
+        key = (self.compute_dtype, dev, tuple(p._version for p in self.parameters()), self.codebook.embeddings._version)
         if self._prepared is not None and self._prepared["key"] == key:
             return self._prepared
         dt = self.compute_dtype
@@ -309,6 +382,8 @@ class VQGAN(nn.Module):
         cv = self._prepared["convs"][name]
         od = cv.out_dims(dims)
         dev = x.device
+        if self._tape is not None:
+            self._tape[name] = (x, dims, in_mode, out_mode)
         if out_mode == 0:
             out = torch.empty(B, *od, cv.cout, device=dev, dtype=self._tdt())
         elif out_mode == 1:
@@ -339,6 +414,8 @@ class VQGAN(nn.Module):
         g, b = gn.weight.detach().float().contiguous(), gn.bias.detach().float().contiguous()
         check(_lib.load().mebt_op_groupnorm_silu(self._code(), ptr(x), ptr(y), ptr(g), ptr(b), ptr(stats), B, int(np.prod(dims)), Cc,
                                                  cur_stream()))
+        if self._tape is not None:
+            self._tape[id(gn)] = (x, stats, B, dims)
         return y
 
     def _res(self, prefix, mod, x, B, dims):
@@ -408,6 +485,176 @@ class VQGAN(nn.Module):
     def forward(self, x):
         """reconstruction (the inference part of vqgan.py:95-100): decode(encode(x))"""
         return self.decode(self.encode(x))
+
+    # ---- backward of the reconstruction objective (vqgan.py:98-102,183-184 before discriminator_iter_start) on csrc/vqgan_bwd/vqgan_bwd.hip ----------
+    @staticmethod
+    def _fill_desc(x, out, w, B, idims, cin, odims, cout, cls, os_, pi, sm, taps, in_mode, out_mode):
+        d = _Desc()
+        d.in_, d.out, d.w, d.bias, d.resid = ptr(x), ptr(out), ptr(w), None, None
+        d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, idims[0], idims[1], idims[2], cin
+        d.To, d.Ho, d.Wo, d.Cout = odims[0], odims[1], odims[2], cout
+        d.cT, d.cH, d.cW = cls
+        for k in range(3):
+            d.os[k], d.pi[k], d.sm[k] = os_[k], pi[k], sm[k]
+        d.ntaps = len(taps)
+        for j, t in enumerate(taps):
+            d.tap[j][0], d.tap[j][1], d.tap[j][2] = t
+        d.in_mode, d.out_mode = in_mode, out_mode
+        return d
+
+    def _acc(self, param, grad, flags):
+        """autograd's accumulate semantics: `.grad` is created where it is None, else added to"""
+        flags.append(torch.isfinite(grad).all())
+        if param.grad is None:
+            param.grad = grad.to(param.dtype).clone()
+        else:
+            param.grad.add_(grad.to(param.dtype))
+
+    def _conv_wgrad(self, name, x, dy, B, dims, in_mode, dy_mode, inv_scale):
+        """-> (weight gradient in the nn.Module's shape, bias gradient), fp32, the gradient scale removed"""
+        cv = self._prepared["convs"][name]
+        od = cv.out_dims(dims)
+        lib = _lib.load()
+        dws, db = [], None
+        for pi, taps, _ in cv.classes:
+            cls = cv.class_counts(od, pi)
+            d = self._fill_desc(x, dy, None, B, dims, cv.cin, od, cv.cout, cls, cv.os, pi, cv.sm, taps, in_mode, dy_mode)
+            tiles = len(taps) * (-(-cv.cout // 64)) * (-(-cv.cin // 64))
+            nsplit = max(1, min(256, -(-1024 // tiles), -(-B * int(np.prod(cls)) // 32)))
+            nbytes = int(lib.mebt_conv3d_wgrad_scratch_bytes(C.byref(d), nsplit))
+            scratch = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
+            dw = torch.empty(cv.cout, len(taps), cv.cin, device=x.device, dtype=torch.float32)
+            dbc = torch.empty(cv.cout, device=x.device, dtype=torch.float32)
+            check(lib.mebt_op_conv3d_wgrad(self._code(), C.byref(d), ptr(dw), ptr(dbc), inv_scale, nsplit, ptr(scratch), nbytes, cur_stream()))
+            dws.append(dw)
+            db = dbc if db is None else db + dbc
+        return cv.full_weight_grad(dws), db
+
+    def _conv_dgrad(self, name, dy, B, dims, dy_mode=0, add=None, out_fp32=False):
+        """dy (the layer's output gradient in the layout of its forward out_mode) -> dx channels-last [B, *dims, Cin] (+ add)"""
+        cv = self._prepared["convs"][name]
+        plan = cv.dgrad_plan(dims)
+        od = cv.out_dims(dims)
+        lib, dev = _lib.load(), dy.device
+        fz, zd, pd, fr = plan["fz"], plan["zd"], plan["pd"], plan["front"]
+        dyz = torch.empty(B, *zd, cv.cout, device=dev, dtype=self._tdt())
+        check(lib.mebt_op_pad_zero(self._code(), ptr(dy), ptr(dyz), B, *od, *fz, *zd, cv.cout, dy_mode, cur_stream()))
+        whole = all(c["w"] is not None for c in plan["classes"])
+        dxp = (torch.empty if whole else torch.zeros)(B, *pd, cv.cin, device=dev, dtype=torch.float32)
+        for c in plan["classes"]:
+            if c["w"] is None or min(c["cq"]) <= 0:
+                continue
+            d = self._fill_desc(dyz, dxp, c["w"], B, zd, cv.cout, pd, cv.cin, c["cq"], c["os"], c["pi"], c["sm"], c["taps"], 0, 1)
+            check(lib.mebt_op_conv3d(self._code(), C.byref(d), 1 if self.use_mfma else 0, cur_stream()))
+        dx = torch.empty(B, *dims, cv.cin, device=dev, dtype=torch.float32 if out_fp32 else self._tdt())
+        check(lib.mebt_op_halo_fold(self._code(), ptr(dxp), ptr(add), ptr(dx), B, *dims, *pd, *fr, cv.cin, 1 if out_fp32 else 0, cur_stream()))
+        return dx
+
+    def _conv_bwd(self, name, dy, B, tape, inv_scale, flags, need_dx=True, add=None, out_fp32=False):
+        x, dims, in_mode, out_mode = tape[name]
+        mod = self.get_submodule(name)
+        conv = mod.conv if isinstance(mod, SamePadConv3d) else mod.convt
+        dw, db = self._conv_wgrad(name, x, dy, B, dims, in_mode, out_mode, inv_scale)
+        self._acc(conv.weight, dw, flags)
+        if conv.bias is not None:
+            self._acc(conv.bias, db, flags)
+        return self._conv_dgrad(name, dy, B, dims, out_mode, add, out_fp32) if need_dx else None
+
+    def _norm_silu_bwd(self, gn, dy, tape, inv_scale, flags, add=None):
+        x, stats, B, dims = tape[id(gn)]
+        Cc, vox = x.shape[-1], int(np.prod(dims))
+        lib = _lib.load()
+        g, b = gn.weight.detach().float().contiguous(), gn.bias.detach().float().contiguous()
+        dx = torch.empty_like(x)
+        dg, dbt = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
+        nbytes = int(lib.mebt_groupnorm_silu_bwd_scratch_bytes(B, vox, Cc))
+        scratch = torch.empty(max(1, nbytes // 8), device=x.device, dtype=torch.float64)
+        check(lib.mebt_op_groupnorm_silu_bwd(self._code(), ptr(x), ptr(stats), ptr(g), ptr(b), ptr(dy), ptr(add), ptr(dx), ptr(dg), ptr(dbt),
+                                             inv_scale, B, vox, Cc, ptr(scratch), nbytes, cur_stream()))
+        self._acc(gn.weight, dg, flags)
+        self._acc(gn.bias, dbt, flags)
+        return dx
+
+    def _res_bwd(self, prefix, mod, g, B, tape, inv_scale, flags):
+        """backward of x + conv2(silu(norm2(conv1(silu(norm1(x)))))): the skip's gradient is added where norm1's dx is stored"""
+        h = self._conv_bwd(prefix + ".conv2", g, B, tape, inv_scale, flags)
+        h = self._norm_silu_bwd(mod.norm2, h, tape, inv_scale, flags)
+        h = self._conv_bwd(prefix + ".conv1", h, B, tape, inv_scale, flags)
+        return self._norm_silu_bwd(mod.norm1, h, tape, inv_scale, flags, add=g)
+
+    def default_grad_scale(self, n_video, n_z):
+        """the power of two S that puts the L1 seed S * l1_weight / numel(x) into (2^-4, 2^-3]; with l1_weight 0, the
+        quantiser seed's factor 0.5 / numel(z) instead"""
+        c = float(self._hp("l1_weight", 4.0)) / n_video
+        if c <= 0.0:
+            c = 0.5 / n_z
+        return 2.0 ** math.floor(math.log2(0.125 / c))
+
+    def recon_backward(self, x, grad_scale=None):
+        """The autoencoder objective of the reference before `discriminator_iter_start` with `perceptual_weight` 0 (vqgan.py:98-102,183-184):
+        loss = l1_weight * mean |x_recon - x| + 0.25 * mse(z, e.detach()), the codebook frozen, the quantiser straight-through
+        (codebook.py:64,91).  Runs the training forward (`encode` + `decode` recording every convolution's input, every GroupNorm's
+        input and statistics, z and the ids), then the backward on the operators of csrc/vqgan_bwd/vqgan_bwd.hip, and ADDS the fp32 gradient to
+        `.grad` of every parameter of encoder, decoder, pre_vq_conv and post_vq_conv (created where None: autograd's semantics, so
+        `optimizer.zero_grad()` works as usual).  The backward is seeded with the power-of-two `grad_scale` S (None:
+        `default_grad_scale`), removed exactly in the fp32 epilogues of the parameter-gradient kernels: in f16 mode the activation
+        gradients are stored as fp16 and the unscaled seed l1_weight / numel(x) lies below fp16's range.
+        -> {recon_loss, commitment_loss, perplexity (0-dim float64 on the device), encodings, grad_scale, finite, x_recon (the
+        reconstruction the L1 seed's signs were taken from)}"""
+        if float(self._hp("perceptual_weight", 0.0)) > 0.0:
+            raise NotImplementedError("recon_backward: perceptual_weight > 0 needs the LPIPS backward, which belongs to the follow-up that "
+                                      "completes first-stage training (EMA codebook, LPIPS backward, discriminators); set perceptual_weight to 0")
+        from . import recon
+        self._prepare()
+        lib = _lib.load()
+        x = x.to(torch.float32).contiguous()
+        B = x.shape[0]
+        self._tape = {}
+        try:
+            ids = self.encode(x)
+            z = self._last_z
+            rec = self.decode(ids)
+        finally:
+            tape, self._tape = self._tape, None
+        emb = self._prepared["emb"]
+        hist, sq_sum = recon.code_stats(ids, z, emb)
+        l1w = float(self._hp("l1_weight", 4.0))
+        out = {"recon_loss": recon.abs_diff_sum(x.view(B, -1), rec.view(B, -1)).sum() / rec.numel() * l1w,
+               "commitment_loss": 0.25 * sq_sum[0] / z.numel(), "perplexity": recon.perplexity_of(hist), "encodings": ids, "x_recon": rec}
+        S = float(grad_scale) if grad_scale is not None else self.default_grad_scale(rec.numel(), z.numel())
+        if not (S > 0.0 and math.isfinite(S) and math.frexp(S)[0] == 0.5):
+            raise ValueError(f"recon_backward: grad_scale must be a positive power of two, got {grad_scale}")
+        inv, flags = 1.0 / S, []
+        with torch.no_grad():
+            seed = torch.empty_like(rec)
+            check(lib.mebt_op_l1_seed(ptr(rec), ptr(x), ptr(seed), rec.numel(), S * l1w / rec.numel(), cur_stream()))
+            g = self._conv_bwd("decoder.conv_last", seed, B, tape, inv, flags)
+            for i in reversed(range(len(self.decoder.conv_blocks))):
+                blk = self.decoder.conv_blocks[i]
+                g = self._res_bwd(f"decoder.conv_blocks.{i}.res2", blk.res2, g, B, tape, inv, flags)
+                g = self._res_bwd(f"decoder.conv_blocks.{i}.res1", blk.res1, g, B, tape, inv, flags)
+                g = self._conv_bwd(f"decoder.conv_blocks.{i}.up", g, B, tape, inv, flags)
+            g = self._norm_silu_bwd(self.decoder.final_block[0], g, tape, inv, flags)
+            g_st = self._conv_bwd("post_vq_conv", g, B, tape, inv, flags, out_fp32=True)       # straight-through: lands on z
+            dz = torch.empty_like(z)
+            check(lib.mebt_op_vq_seed(ptr(z), ptr(emb), ptr(ids), ptr(g_st), ptr(dz), ids.numel(), self.embedding_dim, self.n_codes,
+                                      S * 0.5 / z.numel(), cur_stream()))
+            g = self._conv_bwd("pre_vq_conv", dz, B, tape, inv, flags)
+            g = self._norm_silu_bwd(self.encoder.final_block[0], g, tape, inv, flags)
+            for i in reversed(range(len(self.encoder.conv_blocks))):
+                g = self._res_bwd(f"encoder.conv_blocks.{i}.res", self.encoder.conv_blocks[i].res, g, B, tape, inv, flags)
+                g = self._conv_bwd(f"encoder.conv_blocks.{i}.down", g, B, tape, inv, flags)
+            self._conv_bwd("encoder.conv_first", g, B, tape, inv, flags, need_dx=False)        # the video needs no gradient
+            out["grad_scale"] = S
+            out["finite"] = bool(torch.stack(flags).all().item())
+        return out
+
+    def configure_optimizers(self):
+        """the reference's autoencoder optimizer (vqgan.py:198-206; the codebook has buffers, no parameters); the discriminators'
+        optimizer belongs to the follow-up"""
+        params = (list(self.encoder.parameters()) + list(self.decoder.parameters()) + list(self.pre_vq_conv.parameters())
+                  + list(self.post_vq_conv.parameters()) + list(self.codebook.parameters()))
+        return torch.optim.Adam(params, lr=self._hp("lr", 3e-4), betas=(0.5, 0.9))
 
     # ---- validation (vqgan.py:190-196) on the metric operators of csrc/recon/recon.hip ---------------------------------------------------
     def _hp(self, name, default):
