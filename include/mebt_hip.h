@@ -437,6 +437,31 @@ int mebt_op_clip_quality_u8(const uint8_t* a, const uint8_t* b, int64_t* sq_err,
  * embedding is never read.  scratch: 8 * ceil(M / MEBT_RECON_CODE_ROWS) bytes. */
 int mebt_op_code_stats(const int64_t* ids, const float* z, const float* embeddings, int64_t* hist, double* sq_sum, int64_t M,
                        int32_t n_codes, int32_t d, void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+/* ---- EMA codebook of first-stage training (reference mebt/modules/codebook.py:25-46,66-89; csrc/codebook/codebook_train.hip) ------
+ * All three operators are bitwise reproducible: integer atomics only, every floating-point sum in a fixed order.  The update's
+ * products, sums and quotients are separately rounded fp32 operations in the reference's order (no FMA contraction).  `scratch`
+ * needs 16-byte alignment and the bytes the *_scratch_bytes function states (checked before anything is launched). */
+int64_t mebt_codebook_sums_scratch_bytes(int64_t M, int32_t n_codes);
+/* ids int64 [M], z fp32 [M, d] channels-last (what the codebook search read).  n_total[c] = the number of rows with id c (fp32
+ * [n_codes]), encode_sum[c, :] = the sum of those rows of z (fp32 [n_codes, d]; zero for a code without rows): codebook.py:68-69
+ * without the one-hot matrix.  An inverted index (histogram, exclusive scan, row list per code) is built with integer atomics in
+ * `scratch`; one wave then adds a code's rows in ascending row order in fp32.  Ids outside [0, n_codes) are skipped.  Any d >= 1;
+ * 16-byte loads where d % 4 == 0 and z / encode_sum are 16-byte aligned.  M < 2^31 - 256. */
+int mebt_op_codebook_sums(const int64_t* ids, const float* z, float* n_total, float* encode_sum, int64_t M, int32_t n_codes, int32_t d,
+                          void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+int64_t mebt_codebook_ema_scratch_bytes(int32_t n_codes);
+/* In place, all fp32: N = 0.99 N + 0.01 n_total; z_avg = 0.99 z_avg + 0.01 encode_sum; n = sum N (fixed-order tree);
+ * weights = (N + 1e-7) / (n + n_codes * 1e-7) * n; embeddings = z_avg / weights; and, where k_rand [n_codes, d] is not NULL,
+ * usage = N >= restart_thres, embeddings = embeddings * usage + k_rand * (1 - usage) (codebook.py:74-80,87-89).  restarted[0]
+ * (int32, on the device) = the number of codes with usage 0, 0 without k_rand. */
+int mebt_op_codebook_ema(float* N, float* z_avg, float* embeddings, const float* n_total, const float* encode_sum, const float* k_rand,
+                         int32_t* restarted, int32_t n_codes, int32_t d, float restart_thres, void* scratch, int64_t scratch_bytes,
+                         mebt_stream_t stream);
+/* out[j, :] = z[src[j] mod M, :] + noise[j, :] * std, std = 0.01 / sqrt(d) rounded to fp32, the product rounded before the sum
+ * (codebook.py:25-32,41,83: row src[j] of the tiled and permuted z); noise NULL: the plain rows (M >= n_codes, no tiling).  z fp32
+ * [M, d], src int64 [n_codes], noise / out fp32 [n_codes, d]. */
+int mebt_op_codebook_restart_rows(const float* z, const int64_t* src, const float* noise, float* out, int64_t M, int32_t n_codes, int32_t d,
+                                  mebt_stream_t stream);
 /* ---- Inception-I3D forward for FVD / KVD (reference mebt/fvd/pytorch_i3d.py, mebt/fvd/fvd.py) ---------------------------------
  * Activations are channels-last [B, T, H, W, C] of `dtype` (MEBT_DTYPE_F16: MFMA fast mode, MEBT_DTYPE_F32: parity mode).
  * Uint8 frames [N, H, W, 3] -> bilinear resize to [N, Ho, Wo, 3] (align_corners=False, source coordinate clamped at 0), then

@@ -101,6 +101,11 @@ PROTOTYPES = {
     "mebt_op_abs_diff_sum": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "mebt_op_clip_quality_u8": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mebt_op_code_stats": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_codebook_sums_scratch_bytes": (c_i64, [c_i64, c_i32]),
+    "mebt_op_codebook_sums": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_codebook_ema_scratch_bytes": (c_i64, [c_i32]),
+    "mebt_op_codebook_ema": (c_i32, [c_vp] * 7 + [c_i32, c_i32, c_f32, c_vp, c_i64, c_vp]),
+    "mebt_op_codebook_restart_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "mebt_op_lpips_input": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, C.POINTER(c_f32), C.POINTER(c_f32), c_vp]),
     "mebt_op_conv2d_3x3": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 6 + [c_vp]),
     "mebt_op_maxpool_2x2": (c_i32, [c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),

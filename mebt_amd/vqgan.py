@@ -2,10 +2,11 @@
 operators of csrc/vqgan.hip.  Same constructor argument (`args` namespace with n_hiddens / downsample / image_channels /
 embedding_dim / n_codes), module tree and state-dict names (`encoder.conv_first.conv.weight`, `encoder.conv_blocks.0.res.norm1.weight`,
 `decoder.conv_blocks.0.up.convt.weight`, `pre_vq_conv.conv.weight`, `codebook.embeddings`, ...) so reference checkpoints load;
-the discriminators, the EMA codebook update and the perceptual term's backward are not built (their keys are ignored on load): of
+the discriminators and the perceptual term's backward are not built (their keys are ignored on load): of
 first-stage training, `recon_backward` gives the gradients of recon_loss + commitment_loss (vqgan.py:98-102,183-184 before
-discriminator_iter_start, perceptual_weight 0) on the kernels of csrc/vqgan_bwd/vqgan_bwd.hip with the codebook frozen, and `configure_optimizers`
-the reference's autoencoder Adam; the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
+discriminator_iter_start, perceptual_weight 0) on the kernels of csrc/vqgan_bwd/vqgan_bwd.hip, with the codebook frozen or, with
+`update_codebook=True`, trained by the EMA update with random restarts of modules/codebook.py on csrc/codebook/codebook_train.hip;
+`configure_optimizers` is the reference's autoencoder Adam and `train_step` one step of the two (python -m mebt_amd.train_vqgan); the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
 (vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric operators of csrc/recon/recon.hip
 (mebt_amd/recon.py) and, when the checkpoint carried the perceptual weights, csrc/lpips/lpips.hip.
 
@@ -124,7 +125,11 @@ class Decoder(nn.Module):
 
 
 class Codebook(nn.Module):
-    """buffers of reference modules/codebook.py:13-24; inference only (no EMA update / random restart)"""
+    """buffers of reference modules/codebook.py:13-24.  `update` is the EMA update with random restarts of codebook.py:66-89 and
+    `init_from` the data-dependent initialisation of codebook.py:34-46, both on the operators of csrc/codebook/codebook_train.hip and
+    in place on the three buffers.  `_epoch` counts the in-place rewrites of `embeddings` (a kernel that writes through a raw pointer
+    does not move the tensor's version counter): `VQGAN._prepare` keys on it.  Nothing here runs unless it is called: `VQGAN.encode`
+    never initialises or updates (in the reference, `forward` in training mode does both)."""
 
     def __init__(self, n_codes, embedding_dim, no_random_restart=False, restart_thres=1.0):
         super().__init__()
@@ -132,7 +137,91 @@ class Codebook(nn.Module):
         self.register_buffer('N', torch.zeros(n_codes))
         self.register_buffer('z_avg', self.embeddings.data.clone())
         self.n_codes, self.embedding_dim = n_codes, embedding_dim
+        self._need_init = True
+        self.no_random_restart = no_random_restart
+        self.restart_thres = restart_thres
+        self._epoch = 0
+
+    def _rows(self, who, z):
+        if not torch.is_tensor(z) or z.dtype != torch.float32 or not z.is_cuda or z.numel() == 0 or z.shape[-1] != self.embedding_dim:
+            raise ValueError(f"Codebook.{who}: z must be float32 [..., {self.embedding_dim}] (channels-last) on the GPU, got "
+                             f"{getattr(z, 'dtype', type(z))} {tuple(getattr(z, 'shape', ()))}")
+        for name in ("embeddings", "N", "z_avg"):
+            b = getattr(self, name)
+            if b.dtype != torch.float32 or b.device != z.device or not b.is_contiguous():
+                raise ValueError(f"Codebook.{who}: buffer `{name}` must be contiguous float32 on {z.device}")
+        return z.contiguous().view(-1, self.embedding_dim)
+
+    def restart_rows(self, z, restart_src=None, restart_noise=None, generator=None):
+        """`_k_rand` of codebook.py:41,82-83: n_codes rows of the tiled, noised and permuted z.  z fp32 [M, d].  With R = ceil(n_codes / M)
+        copies of z when M < n_codes (else 1), row j is z[src[j] mod M] + noise[j] * 0.01 / sqrt(d), the noise only when M < n_codes
+        (`_tile`).  restart_src int64 [n_codes] with values in [0, R M) and restart_noise fp32 [n_codes, d] inject the draws (the parity
+        tests: src = the reference's randperm[:n_codes], noise = the rows of its randn_like at those positions); None: drawn here on
+        the device with `generator`."""
+        z = self._rows("restart_rows", z)
+        M, dev = z.shape[0], z.device
+        tiled = M < self.n_codes
+        R = -(-self.n_codes // M) if tiled else 1
+        if restart_src is None:
+            restart_src = torch.randperm(R * M, device=dev, generator=generator)[:self.n_codes]
+        src = restart_src.to(dev, torch.int64).contiguous()
+        if tuple(src.shape) != (self.n_codes,):
+            raise ValueError(f"Codebook.restart_rows: restart_src must hold {self.n_codes} row numbers, got {tuple(src.shape)}")
+        noise = None
+        if tiled:
+            if restart_noise is None:
+                restart_noise = torch.randn(self.n_codes, self.embedding_dim, device=dev, dtype=torch.float32, generator=generator)
+            noise = restart_noise.to(dev, torch.float32).contiguous()
+            if tuple(noise.shape) != (self.n_codes, self.embedding_dim):
+                raise ValueError(f"Codebook.restart_rows: restart_noise must be [{self.n_codes}, {self.embedding_dim}], got {tuple(noise.shape)}")
+        out = torch.empty(self.n_codes, self.embedding_dim, device=dev, dtype=torch.float32)
+        check(_lib.load().mebt_op_codebook_restart_rows(ptr(z), ptr(src), ptr(noise), ptr(out), M, self.n_codes, self.embedding_dim, cur_stream()))
+        return out
+
+    @torch.no_grad()
+    def init_from(self, z, restart_src=None, restart_noise=None, generator=None):
+        """codebook.py:34-46: embeddings = z_avg = restart rows of z, N = 1; clears `_need_init`"""
+        k_rand = self.restart_rows(z, restart_src, restart_noise, generator)
+        self.embeddings.copy_(k_rand)
+        self.z_avg.copy_(k_rand)
+        self.N.fill_(1.0)
         self._need_init = False
+        self._epoch += 1
+
+    @staticmethod
+    def code_sums(ids, z, n_codes):
+        """ids int64 [M], z fp32 [M, d] on the GPU -> (n_total fp32 [n_codes], encode_sum fp32 [n_codes, d]): codebook.py:68-69"""
+        M, d = z.shape
+        lib = _lib.load()
+        n_total = torch.empty(n_codes, device=z.device, dtype=torch.float32)
+        encode_sum = torch.empty(n_codes, d, device=z.device, dtype=torch.float32)
+        nbytes = int(lib.mebt_codebook_sums_scratch_bytes(M, n_codes))
+        scratch = torch.empty(max(1, -(-nbytes // 8)), device=z.device, dtype=torch.float64)
+        check(lib.mebt_op_codebook_sums(ptr(ids), ptr(z), ptr(n_total), ptr(encode_sum), M, n_codes, d, ptr(scratch), nbytes, cur_stream()))
+        return n_total, encode_sum
+
+    @torch.no_grad()
+    def update(self, z, ids, restart_src=None, restart_noise=None, generator=None):
+        """The EMA update of codebook.py:66-89 for one batch: z fp32 [..., d] channels-last (what the search read), ids int64, one per
+        row.  -> the number of codes restarted (0-dim int32 on the device; 0 with `no_random_restart`).  The draws: `restart_rows`."""
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("Codebook.update on several ranks needs the all-reduces of n_total and encode_sum and the broadcast of "
+                                      "the restart rows (codebook.py:70-72,84-85): data-parallel first-stage training is not built")
+        z = self._rows("update", z)
+        ids = ids.reshape(-1).contiguous()
+        if ids.dtype != torch.int64 or ids.device != z.device or ids.numel() != z.shape[0]:
+            raise ValueError(f"Codebook.update: {z.shape[0]} rows of z need as many int64 ids on {z.device}, got {ids.dtype} {tuple(ids.shape)}")
+        lib = _lib.load()
+        n_total, encode_sum = self.code_sums(ids, z, self.n_codes)
+        k_rand = None if self.no_random_restart else self.restart_rows(z, restart_src, restart_noise, generator)
+        restarted = torch.empty(1, device=z.device, dtype=torch.int32)
+        nbytes = int(lib.mebt_codebook_ema_scratch_bytes(self.n_codes))
+        scratch = torch.empty(max(1, -(-nbytes // 8)), device=z.device, dtype=torch.float64)
+        check(lib.mebt_op_codebook_ema(ptr(self.N), ptr(self.z_avg), ptr(self.embeddings), ptr(n_total), ptr(encode_sum), ptr(k_rand),
+                                       ptr(restarted), self.n_codes, self.embedding_dim, float(self.restart_thres), ptr(scratch), nbytes,
+                                       cur_stream()))
+        self._epoch += 1
+        return restarted[0]
 
     def dictionary_lookup(self, encodings):
         """codebook.py:99-101 -> [..., embedding_dim] fp32"""
@@ -286,7 +375,8 @@ class VQGAN(nn.Module):
         self.enc_out_ch = self.encoder.out_channels
         self.pre_vq_conv = SamePadConv3d(self.enc_out_ch, args.embedding_dim, 1, padding_type=padding_type)
         self.post_vq_conv = SamePadConv3d(args.embedding_dim, self.enc_out_ch, 1)
-        self.codebook = Codebook(args.n_codes, args.embedding_dim)
+        self.codebook = Codebook(args.n_codes, args.embedding_dim, no_random_restart=bool(getattr(args, "no_random_restart", False)),
+                                 restart_thres=float(getattr(args, "restart_thres", 1.0)))
         self.compute_dtype = "f16"
         self.use_mfma = True
         self._prepared = None
@@ -320,6 +410,8 @@ class VQGAN(nn.Module):
             own = _lpips.extract({k: v for k, v in state_dict.items() if k.startswith(_lpips.PREFIX)})
             if own is not None:
                 self.lpips_weights = own
+        if "codebook.embeddings" in sd:
+            self.codebook._need_init = False         # trained codes are kept on resume (the reference re-initialises them)
         return super().load_state_dict(sd, strict=strict, **kw)
 
     @property
@@ -354,6 +446,9 @@ class VQGAN(nn.Module):
         # the parameters' version counters: an optimizer step (an in-place update) makes the re-laid-out weights stale
         key = (self.compute_dtype, dev, tuple(p._version for p in self.parameters()), self.codebook.embeddings._version)
         if self._prepared is not None and self._prepared["key"] == key:
+            if self._prepared["emb_epoch"] != self.codebook._epoch:          # Codebook.update / init_from rewrote the codes in place
+                self._prepared["emb"] = self.codebook.embeddings.detach().to(torch.float32).contiguous()
+                self._prepared["emb_epoch"] = self.codebook._epoch
             return self._prepared
         dt = self.compute_dtype
         prep = {"key": key, "convs": {}}
@@ -367,6 +462,7 @@ class VQGAN(nn.Module):
             if isinstance(mod, (SamePadConv3d, SamePadConvTranspose3d)):
                 prep["convs"][name] = conv(mod)
         prep["emb"] = self.codebook.embeddings.detach().to(torch.float32).contiguous()
+        prep["emb_epoch"] = self.codebook._epoch
         self._prepared = prep
         return prep
 
@@ -431,6 +527,15 @@ class VQGAN(nn.Module):
     def encode(self, x, include_embeddings=False):
         """VQGAN.encode (vqgan.py:82-88): x [B, C, T, H, W] float -> encodings [B, t, h, w] int64 (and, with include_embeddings,
         the quantised embeddings [B, c, t, h, w] first)"""
+        z, B, dims = self._encode_z(x)
+        ids = self._search(z).view(B, *dims)
+        if include_embeddings:
+            e = self.codebook.dictionary_lookup(ids)                                     # [B, t, h, w, c]
+            return e.permute(0, 4, 1, 2, 3), ids                                         # a view: [B, c, t, h, w] (shift_dim, codebook.py:63)
+        return ids
+
+    def _encode_z(self, x):
+        """pre_vq_conv(encoder(x)) -> (z fp32 [B, t, h, w, c], B, (t, h, w)); kept in `_last_z`"""
         self._prepare()
         x = x.to(torch.float32).contiguous()
         B, dims = x.shape[0], tuple(x.shape[2:])
@@ -440,27 +545,27 @@ class VQGAN(nn.Module):
             h = self._res(f"encoder.conv_blocks.{i}.res", blk.res, h, B, dims)
         h = self._norm_silu(self.encoder.final_block[0], h, B, dims)
         z, dims = self._conv("pre_vq_conv", h, B, dims, out_mode=1)                    # fp32 [B, t, h, w, c] for the search
-        M = B * int(np.prod(dims))
-        emb = self._prepared["emb"]
-        esq = torch.empty(self.n_codes + 1, device=x.device, dtype=torch.float32)
-        ids = torch.empty(M, device=x.device, dtype=torch.long)
+        self._last_z = z
+        return z, B, dims
+
+    def _search(self, z):
+        """the arg-min of codebook.py:53-57 over the prepared codes -> ids int64 [M]"""
+        M = z.numel() // self.embedding_dim
+        emb = self._prepare()["emb"]
+        esq = torch.empty(self.n_codes + 1, device=z.device, dtype=torch.float32)
+        ids = torch.empty(M, device=z.device, dtype=torch.long)
         # large searches (config 5 at batch 16: 16384 x 16384 x 256): approximate scores on the bf16 MFMA GEMM + exact fp32 re-evaluation
         # of every code that can still be the arg-min (csrc/vqgan.hip codebook_filter_kernel); small ones: the exact fp32 GEMM directly
         if (self.use_mfma and self.embedding_dim % 64 == 0 and self.n_codes % 8 == 0 and M * self.n_codes >= (1 << 24)
                 and os.environ.get("MEBT_CODEBOOK_FILTER", "1") != "0"):
-            lowp = torch.empty((M + self.n_codes) * self.embedding_dim, device=x.device, dtype=torch.bfloat16)
-            score = torch.empty(M, self.n_codes, device=x.device, dtype=torch.bfloat16)     # approximate scores: half the bytes of the exact path's matrix
+            lowp = torch.empty((M + self.n_codes) * self.embedding_dim, device=z.device, dtype=torch.bfloat16)
+            score = torch.empty(M, self.n_codes, device=z.device, dtype=torch.bfloat16)     # approximate scores: half the bytes of the exact path's matrix
             check(_lib.load().mebt_op_codebook_argmin_filtered(ptr(z), ptr(emb), ptr(score), ptr(esq), ptr(lowp), ptr(ids), M, self.n_codes,
                                                                self.embedding_dim, cur_stream()))
         else:
-            score = torch.empty(M, self.n_codes, device=x.device, dtype=torch.float32)
+            score = torch.empty(M, self.n_codes, device=z.device, dtype=torch.float32)
             check(_lib.load().mebt_op_codebook_argmin(ptr(z), ptr(emb), ptr(score), ptr(esq), ptr(ids), M, self.n_codes, self.embedding_dim,
                                                       cur_stream()))
-        self._last_z = z
-        ids = ids.view(B, *dims)
-        if include_embeddings:
-            e = self.codebook.dictionary_lookup(ids)                                     # [B, t, h, w, c]
-            return e.permute(0, 4, 1, 2, 3), ids                                         # a view: [B, c, t, h, w] (shift_dim, codebook.py:63)
         return ids
 
     @torch.no_grad()
@@ -590,7 +695,8 @@ class VQGAN(nn.Module):
             c = 0.5 / n_z
         return 2.0 ** math.floor(math.log2(0.125 / c))
 
-    def recon_backward(self, x, grad_scale=None):
+    def recon_backward(self, x, grad_scale=None, update_codebook=False, restart_src=None, restart_noise=None, init_src=None, init_noise=None,
+                       generator=None):
         """The autoencoder objective of the reference before `discriminator_iter_start` with `perceptual_weight` 0 (vqgan.py:98-102,183-184):
         loss = l1_weight * mean |x_recon - x| + 0.25 * mse(z, e.detach()), the codebook frozen, the quantiser straight-through
         (codebook.py:64,91).  Runs the training forward (`encode` + `decode` recording every convolution's input, every GroupNorm's
@@ -600,10 +706,20 @@ class VQGAN(nn.Module):
         `default_grad_scale`), removed exactly in the fp32 epilogues of the parameter-gradient kernels: in f16 mode the activation
         gradients are stored as fp16 and the unscaled seed l1_weight / numel(x) lies below fp16's range.
         -> {recon_loss, commitment_loss, perplexity (0-dim float64 on the device), encodings, grad_scale, finite, x_recon (the
-        reconstruction the L1 seed's signs were taken from)}"""
+        reconstruction the L1 seed's signs were taken from)}
+
+        update_codebook (default False: the codebook stays frozen, as above) trains the codebook too, as the reference's forward does in
+        training mode: while `codebook._need_init` is set, `Codebook.init_from(z)` runs after the encoder and before the arg-min
+        (codebook.py:50-51), and `Codebook.update(z, ids)` runs after `mebt_op_vq_seed`, so that the commitment loss, the straight-through
+        gradient and the decoder's input all use the codes from BEFORE the update (in the reference `F.embedding` has copied them by
+        then).  The dict gains `codes_restarted` (0-dim int32 on the device).  restart_src / restart_noise and init_src / init_noise inject
+        the draws of the update and of the initialisation (`Codebook.restart_rows`); `generator` seeds those drawn here."""
         if float(self._hp("perceptual_weight", 0.0)) > 0.0:
             raise NotImplementedError("recon_backward: perceptual_weight > 0 needs the LPIPS backward, which belongs to the follow-up that "
                                       "completes first-stage training (EMA codebook, LPIPS backward, discriminators); set perceptual_weight to 0")
+        if update_codebook and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("recon_backward(update_codebook=True) on several ranks needs the all-reduces of n_total and encode_sum and "
+                                      "the broadcast of the restart rows (codebook.py:70-72,84-85): data-parallel first-stage training is not built")
         from . import recon
         self._prepare()
         lib = _lib.load()
@@ -611,8 +727,11 @@ class VQGAN(nn.Module):
         B = x.shape[0]
         self._tape = {}
         try:
-            ids = self.encode(x)
-            z = self._last_z
+            with torch.no_grad():
+                z, _, dims = self._encode_z(x)
+                if update_codebook and self.codebook._need_init:
+                    self.codebook.init_from(z, init_src, init_noise, generator)
+                ids = self._search(z).view(B, *dims)
             rec = self.decode(ids)
         finally:
             tape, self._tape = self._tape, None
@@ -639,6 +758,8 @@ class VQGAN(nn.Module):
             dz = torch.empty_like(z)
             check(lib.mebt_op_vq_seed(ptr(z), ptr(emb), ptr(ids), ptr(g_st), ptr(dz), ids.numel(), self.embedding_dim, self.n_codes,
                                       S * 0.5 / z.numel(), cur_stream()))
+            if update_codebook:                        # after the last reader of the old codes; nothing below reads the codebook
+                out["codes_restarted"] = self.codebook.update(z, ids, restart_src, restart_noise, generator)
             g = self._conv_bwd("pre_vq_conv", dz, B, tape, inv, flags)
             g = self._norm_silu_bwd(self.encoder.final_block[0], g, tape, inv, flags)
             for i in reversed(range(len(self.encoder.conv_blocks))):
@@ -647,6 +768,19 @@ class VQGAN(nn.Module):
             self._conv_bwd("encoder.conv_first", g, B, tape, inv, flags, need_dx=False)        # the video needs no gradient
             out["grad_scale"] = S
             out["finite"] = bool(torch.stack(flags).all().item())
+        return out
+
+    def train_step(self, x, optimizer, grad_scale=None, **draws):
+        """one step of the reference's recipe before `discriminator_iter_start` with `perceptual_weight` 0: `optimizer.zero_grad()`,
+        `recon_backward(x, update_codebook=True)`, `optimizer.step()` -> recon_backward's dict.  A non-finite gradient raises before the
+        optimizer step (the codebook has been updated by then: it saw only the forward).  `draws`: recon_backward's restart_src /
+        restart_noise / init_src / init_noise / generator."""
+        optimizer.zero_grad()
+        out = self.recon_backward(x, grad_scale=grad_scale, update_codebook=True, **draws)
+        if not out["finite"]:
+            raise FloatingPointError(f"train_step: a gradient is not finite at grad_scale {out['grad_scale']:g}; the optimizer step was not taken "
+                                     "(pass a smaller power-of-two grad_scale)")
+        optimizer.step()
         return out
 
     def configure_optimizers(self):
