@@ -522,6 +522,35 @@ int mebt_op_maxpool_2x2(int32_t dtype, const void* in, void* out, int32_t N, int
  * float atomics, the same bits on every run.  scratch: 8-byte aligned, 8 * N * ceil(P / MEBT_LPIPS_HEAD_ROWS) bytes. */
 int mebt_op_lpips_head(int32_t dtype, const void* feats, const float* w, double* out, double* layer_out, int64_t layer_stride, int64_t N,
                        int64_t P, int32_t C, void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+/* ---- LPIPS backward: the perceptual term of first-stage training (csrc/lpips/lpips_bwd.hip; LPIPS.value_and_grad) -------
+ * The network is frozen: data gradients only.  Same layouts and dtypes as the forward; arithmetic in fp32, stores in `dtype`.  No float
+ * atomics and no reduction whose order depends on the launch: the same bits on every run, and an image's gradient does not depend on the
+ * batch it ran in. */
+/* Backward of one slice's term, for the reconstruction half only.  feats [2 N, P, C] and w as mebt_op_lpips_head reads them; add
+ * [N, P, C] (may be NULL): the gradient arriving from the deeper slice through the next pool.  With d = |f| + 1e-10, k = -2 coef / P
+ * (rounded to fp32 once on the host):  g_c = k w_c (f0_c / d0 - f1_c / d1),  df1_c = g_c / d1 - f1_c (sum_k g_k f1_k) / (|f1| d1^2)
+ * (the second term 0 where |f1| = 0);  d_feats[n, p, c] = f1_c > 0 ? df1_c + add : 0 (the slice output is a ReLU output, so this is the
+ * gradient at the last convolution's pre-activation).  One wave per pixel. */
+int mebt_op_lpips_head_bwd(int32_t dtype, const void* feats, const float* w, const void* add, void* d_feats, int64_t N, int64_t P, int32_t C,
+                           double coef, mebt_stream_t stream);
+/* nn.MaxPool2d(2, 2) backward: in [N, H, W, C] (the pool's saved input, a ReLU output), dy [N, H / 2, W / 2, C] -> dx [N, H, W, C], every
+ * element written (zeros in a trailing odd row or column).  dy goes to the first maximum of its window in row-major order (torch's
+ * rule) where that maximum is positive; a window of zeros passes nothing on. */
+int mebt_op_maxpool_2x2_bwd(int32_t dtype, const void* in, const void* dy, void* dx, int32_t N, int32_t H, int32_t W, int32_t C,
+                            mebt_stream_t stream);
+/* Data gradient of mebt_op_conv2d_3x3: dy [N, H, W, Cin] (Cin = the forward's Cout, a multiple of 32 up to 512) -> dx [N, H, W, Cout]
+ * (Cout = the forward's Cin, any value >= 1).  w_dgrad: [Cout rounded up to 64][Kpad] with the taps flipped and the channels swapped
+ * (mebt_amd.lpips.arrange_weight_dgrad).  It is the forward's kernel without bias and ReLU; y_prev [N, H, W, Cout] (may be NULL) is the
+ * forward output of the layer below and dx = y_prev > 0 ? acc : 0, the ReLU's backward fused.  All four pointers 16-byte aligned. */
+int mebt_op_conv2d_3x3_dgrad(int32_t dtype, const void* dy, const void* w_dgrad, const void* y_prev, void* dx, int32_t N, int32_t H, int32_t W,
+                             int32_t Cin, int32_t Cout, mebt_stream_t stream);
+/* ScalingLayer backward: seed[b, c, t, y, x] += factor * (d_in[n, y, x, c] / scale[c]) for (b, t) = frames[n].  d_in [n_frames, H, W, 3]
+ * of `dtype`; seed fp32 [B, 3, T, H, W] (what mebt_op_l1_seed writes); the division is rounded in fp32, then multiplied by `factor`, a
+ * positive power of two (exact).  frames: int32 [n_frames][2] on the device; frames_host: the same pairs in HOST memory, which are
+ * checked before the launch: a pair outside the video or a repeated pair is MEBT_STATUS_EINVAL (each seed element has one writer, so the
+ * kernel is a plain read-modify-write).  scale: three floats in HOST memory. */
+int mebt_op_lpips_input_bwd(int32_t dtype, const void* d_in, const int32_t* frames, const int32_t* frames_host, float* seed, int32_t B,
+                            int32_t T, int32_t H, int32_t W, int64_t n_frames, const float* scale, float factor, mebt_stream_t stream);
 
 /* ---- instrumentation ----------------------------------------------------------------------------- */
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py roofline): enable, run,

@@ -11,6 +11,8 @@
 // taps) of the slice at a time; the next stage's operands are fetched into registers while the current one is multiplied.  An
 // output's accumulation order is (slice, dh, dw, channel) whatever the batch, the patch shape or the tile it falls in: no split-K.
 // The first layer (Cin = 3, K = 27 padded to 32) is a kernel of its own: one im2col tile, one K step.
+// The data gradient of training (mebt_op_conv2d_3x3_dgrad; the rest of the backward is lpips_bwd.hip) is the same kernel on flipped,
+// transposed weights, instantiated with MASK: its epilogue keeps a result only where the forward activation below was positive.
 //
 // Head.  One wave per pixel: channel norms and the weighted squared difference in fp32 (at most C / 64 terms per lane between
 // fixed-order butterflies), fp64 from there; one fp64 partial per workgroup in the caller's scratch, added in index order by a
@@ -36,14 +38,16 @@ template <> struct CvCfg<float> { static constexpr int VEC = 4, WM = 1, BM = 64,
 
 struct ConvArgs {
     const void* in; const void* w; const float* bias; void* out;
+    const void* mask;               // MASK kernels only: the output is kept where mask (the output's shape) is positive, else 0
     int N, H, W, Cin, Cout, Kpad, relu;
     int PH, PW, G, PY, PX;          // patch rows / columns, patches per tile, patches per image down / across
     long long NP;                   // patches of the whole batch
 };
 
 // lane's four consecutive output channels n0 + 16 j + 4 fq + (0..3) of one pixel, for j = 0..3
-template <typename T>
-__device__ __forceinline__ void store_pixel(T* o, const f32x4* acc, int n0, int fq, const ConvArgs& p) {
+// MASK (the data gradient, mebt_op_conv2d_3x3_dgrad): m is the pixel of the forward activation below, the ReLU's backward is fused
+template <typename T, bool MASK = false>
+__device__ __forceinline__ void store_pixel(T* o, const f32x4* acc, int n0, int fq, const ConvArgs& p, const T* m = nullptr) {
     const bool vec = (p.Cout & 3) == 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -55,6 +59,9 @@ __device__ __forceinline__ void store_pixel(T* o, const f32x4* acc, int n0, int 
             const int n = nb + r;
             v[r] = acc[j][r] + ((p.bias && n < p.Cout) ? p.bias[n] : 0.f);
             if (p.relu) v[r] = fmaxf(v[r], 0.f);
+            if constexpr (MASK) {
+                if (n < p.Cout && !((float)m[n] > 0.f)) v[r] = 0.f;
+            }
         }
         if (vec) {
             if constexpr (sizeof(T) == 2) *reinterpret_cast<f16x4*>(o + nb) = f16x4{(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
@@ -67,7 +74,7 @@ __device__ __forceinline__ void store_pixel(T* o, const f32x4* acc, int n0, int 
     }
 }
 
-template <typename T, int NPOS>
+template <typename T, int NPOS, bool MASK = false>
 __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
     using Cfg = CvCfg<T>;
     constexpr int VEC = Cfg::VEC, LD = Cfg::LD, WM = Cfg::WM;
@@ -213,7 +220,9 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
         const int r2 = (int)(q - n * ppi), py = r2 / p.PX, px = r2 - py * p.PX;
         const int y = py * p.PH + r, x = px * p.PW + c;
         if (y >= p.H || x >= p.W) continue;
-        store_pixel<T>(out + (size_t)((n * p.H + y) * p.W + x) * (size_t)p.Cout, acc[i], n0, fq, p);
+        const size_t o = (size_t)((n * p.H + y) * p.W + x) * (size_t)p.Cout;
+        if constexpr (MASK) store_pixel<T, true>(out + o, acc[i], n0, fq, p, reinterpret_cast<const T*>(p.mask) + o);
+        else store_pixel<T>(out + o, acc[i], n0, fq, p);
     }
 }
 
@@ -419,11 +428,11 @@ int check_dtype(const char* who, int32_t dtype) {
     return MEBT_OK;
 }
 
-template <typename T>
+template <typename T, bool MASK = false>
 int launch_conv(ConvArgs a, hipStream_t stream) {
     using Cfg = CvCfg<T>;
     const unsigned gy = (unsigned)((a.Cout + CV_BN - 1) / CV_BN);
-    if (a.Cin == 3) {
+    if (!MASK && a.Cin == 3) {
         const long long M = (long long)a.N * a.H * a.W, gx = (M + Cfg::BM - 1) / Cfg::BM;
         if (gx > 0x7FFFFFFFll) return fail(MEBT_ESHAPE, "conv2d_3x3", "too many output pixels for one launch");
         hipLaunchKernelGGL(conv3x3_c3_kernel<T>, dim3((unsigned)gx, gy), dim3(CV_THREADS), 0, stream, a, M);
@@ -441,8 +450,8 @@ int launch_conv(ConvArgs a, hipStream_t stream) {
     if (gx > 0x7FFFFFFFll) return fail(MEBT_ESHAPE, "conv2d_3x3", "too many output pixels for one launch");
     const int npos = a.G * (ph + 2) * (pw + 2);                     // <= 4 BM
     const dim3 grid((unsigned)gx, gy);
-    if (npos <= Cfg::NPOS_SMALL) hipLaunchKernelGGL((conv3x3_kernel<T, Cfg::NPOS_SMALL>), grid, dim3(CV_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((conv3x3_kernel<T, 4 * Cfg::BM>), grid, dim3(CV_THREADS), 0, stream, a);
+    if (npos <= Cfg::NPOS_SMALL) hipLaunchKernelGGL((conv3x3_kernel<T, Cfg::NPOS_SMALL, MASK>), grid, dim3(CV_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL((conv3x3_kernel<T, 4 * Cfg::BM, MASK>), grid, dim3(CV_THREADS), 0, stream, a);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -487,6 +496,27 @@ extern "C" int mebt_op_conv2d_3x3(int32_t dtype, const void* in, const void* w, 
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu != 0;
     a.Kpad = (9 * Cin + CV_BK - 1) / CV_BK * CV_BK;
     return dtype == MEBT_DTYPE_F16 ? launch_conv<f16_t>(a, S(stream)) : launch_conv<float>(a, S(stream));
+}
+
+// The data gradient of the convolution above: the same kernel on `arrange_weight_dgrad`'s weights (taps flipped, channels swapped),
+// no bias, no ReLU; with y_prev the epilogue keeps the result only where the forward activation below was positive.
+extern "C" int mebt_op_conv2d_3x3_dgrad(int32_t dtype, const void* dy, const void* w_dgrad, const void* y_prev, void* dx, int32_t N, int32_t H,
+                                        int32_t W, int32_t Cin, int32_t Cout, mebt_stream_t stream) {
+    const char* who = "conv2d_3x3_dgrad";
+    if (!dy || !w_dgrad || !dx) return fail(MEBT_EINVAL, who, "null pointer");
+    if (int rc = check_dtype(who, dtype)) return rc;
+    if (N < 1 || H < 1 || W < 1 || Cout < 1) return fail(MEBT_ESHAPE, who, "need N, H, W, Cout >= 1");
+    if (H > (1 << 20) || W > (1 << 20)) return fail(MEBT_ESHAPE, who, "map too large");
+    if (!(Cin >= 32 && Cin % 32 == 0 && Cin <= 512)) return fail(MEBT_ESHAPE, who, "need Cin (the forward's Cout) a multiple of 32 up to 512");
+    if (!aligned16(dy) || !aligned16(w_dgrad) || !aligned16(dx) || !aligned16(y_prev))
+        return fail(MEBT_EINVAL, who, "dy, w_dgrad, y_prev and dx must be 16-byte aligned");
+    ConvArgs a{};
+    a.in = dy; a.w = w_dgrad; a.bias = nullptr; a.out = dx; a.mask = y_prev;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = 0;
+    a.Kpad = (9 * Cin + CV_BK - 1) / CV_BK * CV_BK;
+    const bool f16 = dtype == MEBT_DTYPE_F16;
+    if (y_prev) return f16 ? launch_conv<f16_t, true>(a, S(stream)) : launch_conv<float, true>(a, S(stream));
+    return f16 ? launch_conv<f16_t>(a, S(stream)) : launch_conv<float>(a, S(stream));
 }
 
 extern "C" int mebt_op_maxpool_2x2(int32_t dtype, const void* in, void* out, int32_t N, int32_t H, int32_t W, int32_t C, mebt_stream_t stream) {

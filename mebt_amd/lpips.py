@@ -14,10 +14,20 @@ ping-pong activation buffers; pairs are walked in chunks sized to a byte budget,
 of a pair's value (the convolution's accumulation order is fixed per output, the head is reproducible).  `lpips_twin` is the plain
 torch statement of the same definition: what the tests hold the kernels to; the product never calls it.
 
-MEBT_LPIPS_CONV=own|i3d picks the convolution: `own` (default) is mebt_op_conv2d_3x3, `i3d` routes the same prepared weights through
+`LPIPS.value_and_grad` is the perceptual term of first-stage training (`VQGAN.recon_backward` with `perceptual_weight > 0`):
+the same forward with the 13 convolution outputs kept, then the backward into the reconstruction on csrc/lpips/lpips_bwd.hip.  The network
+is frozen, so only data gradients exist:
+
+  lpips_head_bwd     d(slice term)/d(reconstruction features) + the gradient from the deeper slice, masked with the features' sign
+  conv2d_3x3_dgrad   the forward's kernel on flipped, transposed weights (`arrange_weight_dgrad`), the ReLU mask of the layer below fused
+  maxpool_2x2_bwd    the gradient to the first maximum of each window, where it is positive
+  lpips_input_bwd    factor * d / scale added into the fp32 seed video at the chosen frames
+
+MEBT_LPIPS_CONV=own|i3d picks the forward's convolution (`value_and_grad` runs on `own` only): `own` (default) is mebt_op_conv2d_3x3, `i3d` routes the same prepared weights through
 mebt_op_i3d_conv (k = (1, 3, 3)), the gather-per-tap kernel it is measured against (tools/lpips_bench.py).
 """
 import ctypes as C
+import math
 import os
 import types
 
@@ -101,6 +111,31 @@ def arrange_weight(w, dtype):
     return wl.to(dtype).contiguous()
 
 
+def arrange_weight_dgrad(w, dtype):
+    """[Cout, Cin, 3, 3] -> the weights of the data gradient as a forward convolution from Cout to Cin channels: [Cin rounded up to
+    64][Kpad], K = 9 Cout as (tap, co) with co fastest and the taps flipped (dx[y, x] meets dy[y - (dh - 1), x - (dw - 1)] under
+    w[:, :, dh, dw], which is tap (2 - dh, 2 - dw) of a convolution over dy): what mebt_op_conv2d_3x3_dgrad reads"""
+    return arrange_weight(w.flip(2, 3).transpose(0, 1), dtype)
+
+
+# max |d (sum_n LPIPS_n) / d activation| of the float64 twin on the fixture's `full` case (one 128 x 128 pair, closed-form weights):
+# at the scaled input, then at each of the 13 convolution outputs in forward order (tests/golden/lpips_grad/make_golden_lpips_grad.py
+# prints it; DESIGN.md §9g).  Every slice's term is a spatial mean, so the figures fall as 1 / (H W).  Unmeasured on the real VGG weights.
+GRAD_MAX_INPUT = 1.21e-5
+GRAD_MAX_TABLE = (2.29e-6, 4.51e-6, 8.13e-7, 1.10e-6, 2.59e-7, 2.41e-7, 6.10e-7, 1.62e-7, 1.66e-7, 2.44e-7, 2.39e-7, 1.97e-7, 4.55e-7)
+GRAD_TABLE_PIXELS = 128 * 128
+GRAD_TARGET = 2.0 ** 8            # where the branch's largest stored gradient is put: 2^8 below fp16's largest finite value
+
+
+def default_branch_scale(coef, H, W):
+    """the power of two S_p that puts |coef| * S_p * (the largest figure of the table, carried to H x W by 1 / (H W)) at or just below
+    GRAD_TARGET"""
+    top = abs(float(coef)) * max(max(GRAD_MAX_TABLE), GRAD_MAX_INPUT) * GRAD_TABLE_PIXELS / float(H * W)
+    if not (top > 0.0 and math.isfinite(top)):
+        return 1.0
+    return 2.0 ** math.floor(math.log2(GRAD_TARGET / top))
+
+
 def plan_flops(H, W, n_images=1):
     """multiply-add FLOPs (2 per MAC) of the 13 convolutions on `n_images` images of H x W, and the per-layer list"""
     per, h, w, k = [], H, W, 0
@@ -168,6 +203,41 @@ def lpips_head(feats, w, out, n_pairs, P, Cc, scratch, layer_out=None, layer_str
     return out
 
 
+def lpips_head_bwd(feats, w, d_feats, n_pairs, P, Cc, coef, add=None, dtype="f16"):
+    """feats [2 n_pairs, P, Cc] -> d_feats [n_pairs, P, Cc] (written): coef * d(slice term)/d(reconstruction features) + add, masked with
+    the features' sign (include/mebt_hip.h)"""
+    _lib.check(_lib.load().mebt_op_lpips_head_bwd(_code(dtype), _lib.ptr(feats), _lib.ptr(w), _lib.ptr(add), _lib.ptr(d_feats), n_pairs, P, Cc,
+                                                  float(coef), _lib.cur_stream()))
+    return d_feats
+
+
+def maxpool_2x2_bwd(x, dy, dx, dtype="f16"):
+    """x [N, H, W, C] (the pool's input), dy [N, H // 2, W // 2, C] -> dx [N, H, W, C] (every element written)"""
+    N, H, W, Cc = (int(v) for v in x.shape)
+    _lib.check(_lib.load().mebt_op_maxpool_2x2_bwd(_code(dtype), _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dx), N, H, W, Cc, _lib.cur_stream()))
+    return dx
+
+
+def conv2d_3x3_dgrad(dy, w_dgrad, y_prev, dx, cin, cout, dtype="f16"):
+    """dy [N, H, W, cin] (cin: the forward's Cout) -> dx [N, H, W, cout] (written), kept where y_prev > 0 when y_prev is given;
+    w_dgrad from `arrange_weight_dgrad`"""
+    N, H, W = int(dy.shape[0]), int(dy.shape[1]), int(dy.shape[2])
+    _lib.check(_lib.load().mebt_op_conv2d_3x3_dgrad(_code(dtype), _lib.ptr(dy), _lib.ptr(w_dgrad), _lib.ptr(y_prev), _lib.ptr(dx), N, H, W, cin, cout,
+                                                    _lib.cur_stream()))
+    return dx
+
+
+def lpips_input_bwd(d_in, frames, frames_host, seed, scale=SCALE, factor=1.0, dtype="f16"):
+    """seed fp32 [B, 3, T, H, W] += factor * d_in [n, H, W, 3] / scale at the (b, t) of `frames` (int32 [n, 2] on the device;
+    `frames_host` the same tensor on the CPU, checked to hold distinct pairs)"""
+    B, _, T, H, W = (int(v) for v in seed.shape)
+    fh = frames_host.to(torch.int32).contiguous()
+    sc = (C.c_float * 3)(*[float(v) for v in scale])
+    _lib.check(_lib.load().mebt_op_lpips_input_bwd(_code(dtype), _lib.ptr(d_in), _lib.ptr(frames), C.c_void_p(fh.data_ptr()), _lib.ptr(seed), B, T, H,
+                                                   W, int(fh.shape[0]), sc, float(factor), _lib.cur_stream()))
+    return seed
+
+
 class LPIPS:
     """The prepared network on one device.  `sd`: the un-prefixed tensors of `extract`."""
 
@@ -189,6 +259,8 @@ class LPIPS:
         for stem, cin, cout in conv_keys():
             self.convs.append((arrange_weight(sd[stem + ".weight"].to(device), tdt), sd[stem + ".bias"].to(device, torch.float32).contiguous(),
                                cin, cout))
+        self._w_raw = [sd[stem + ".weight"] for stem, _, _ in conv_keys()]       # for the data-gradient weights of `value_and_grad`
+        self._wd = None
         self.lins = [sd[f"lin{k}.model.1.weight"].to(device, torch.float32).reshape(-1).contiguous() for k in range(5)]
         self.shift = [float(v) for v in sd["scaling_layer.shift"]]
         self.scale = [float(v) for v in sd["scaling_layer.scale"]]
@@ -286,6 +358,128 @@ class LPIPS:
         for s in range(0, n, per):
             self._chunk(x, y, pairs[s:s + per], out[s:s + per], None if lay is None else lay[s:s + per], bufs, scratch, tap)
         return (out, lay) if layers else out
+
+    # ---- value and gradient (training: the perceptual term of the first stage) -------------------------------------------
+    def _dgrad_weights(self):
+        """the 13 data-gradient weights, prepared at the first backward"""
+        if self.__dict__.get("_wd") is None:
+            tdt = _tdt(self.dtype)
+            self._wd = [arrange_weight_dgrad(self._w_raw[k].to(self.device), tdt) for k in range(len(self.convs))]
+        return self._wd
+
+    @staticmethod
+    def _tape_elems(H, W):
+        """elements of the 13 convolution outputs of one image, and of the largest of them"""
+        _, per = plan_flops(H, W)
+        sizes = [h * w * cout for (_s, h, w, _ci, cout, _f) in per]
+        return sum(sizes), max(sizes)
+
+    def pairs_per_chunk_grad(self, H, W):
+        es = 2 if self.dtype == "f16" else 4
+        total, widest = self._tape_elems(H, W)
+        # the tape of both images, the pooled input of the running slice (both images), two gradient buffers (one image), the scratch
+        per_pair = es * (2 * total + 2 * widest + 2 * widest) + 8 * (-(-H * W // HEAD_ROWS))
+        return max(1, self.budget_bytes // per_pair)
+
+    def _chunk_grad(self, x, y, frames, frames_host, out, seed, coef_p, factor, scratch, flags, keep):
+        m = int(frames.shape[0])
+        H, W = int(x.shape[3]), int(x.shape[4])
+        tdt, dev = _tdt(self.dtype), self.device
+        # forward, every convolution output kept
+        cur = torch.empty(2 * m, H, W, 3, device=dev, dtype=tdt)
+        lpips_input(x, frames, cur[:m], self.shift, self.scale, self.dtype)
+        lpips_input(y, frames, cur[m:], self.shift, self.scale, self.dtype)
+        tape, dims, last, first = [], [], [], []
+        h, w, c, k = H, W, 3, 0
+        for s, ((_, idxs), cout) in enumerate(zip(SLICE_CONVS, CHANNELS)):
+            if s > 0:
+                nxt = torch.empty(2 * m, h // 2, w // 2, c, device=dev, dtype=tdt)
+                maxpool_2x2(cur, nxt, self.dtype)
+                cur, h, w = nxt, h // 2, w // 2
+            first.append(k)
+            for _i in idxs:
+                nxt = torch.empty(2 * m, h, w, cout, device=dev, dtype=tdt)
+                self._conv(cur, nxt, k)
+                tape.append(nxt)
+                dims.append((h, w))
+                cur, c, k = nxt, cout, k + 1
+            last.append(k - 1)
+            lpips_head(cur, self.lins[s], out, m, h * w, c, scratch, None, 5, self.dtype)
+        del cur, nxt
+        # backward, slice by slice from the deepest
+        wd = self._dgrad_weights()
+        d_feats = [None] * 5
+        add = None
+        for s in reversed(range(5)):
+            kl = last[s]
+            h, w = dims[kl]
+            cc = self.convs[kl][3]
+            g = torch.empty(m, h, w, cc, device=dev, dtype=tdt)
+            lpips_head_bwd(tape[kl], self.lins[s], g, m, h * w, cc, coef_p, add, self.dtype)
+            if keep:
+                d_feats[s] = g
+            for k in range(kl, first[s] - 1, -1):
+                _, _, cin, cout = self.convs[k]
+                y_prev = tape[k - 1][m:] if k > first[s] else None     # below a slice's first convolution lies the pool (or the input)
+                dx = torch.empty(m, h, w, cin, device=dev, dtype=tdt)
+                conv2d_3x3_dgrad(g, wd[k], y_prev, dx, cout, cin, self.dtype)
+                g = dx
+            if s > 0:
+                below = tape[last[s - 1]][m:]
+                add = torch.empty(m, *below.shape[1:], device=dev, dtype=tdt)
+                maxpool_2x2_bwd(below, g, add, self.dtype)
+        flags.append(torch.isfinite(g).all())
+        lpips_input_bwd(g, frames, frames_host, seed, self.scale, factor, self.dtype)
+        return tape, d_feats
+
+    @torch.no_grad()
+    def value_and_grad(self, x, y, frames, seed, coef, grad_scale=None, keep_tape=False, flags=None):
+        """The values of `__call__(x, y, frames)` (float64 [n]), and seed += coef * d(sum_n value_n)/dy.  x, y: the fp32 boundary tensors
+        [B, 3, T, H, W]; `frames`: an int tensor [B] (one frame per clip) or distinct (b, t) pairs; seed: fp32, y's shape, the tensor
+        mebt_op_l1_seed wrote (`coef` already carries its gradient scale).  The forward keeps the 13 convolution outputs of a chunk (a
+        chunk's live bytes stay under `budget_bytes`); the backward is head_bwd at each slice output, the data gradients down the
+        slice's convolutions with the ReLU masks fused, pool_bwd into the slice below, then input_bwd into the seed.  The branch runs at
+        its own power-of-two scale `grad_scale` = S_p (None: `default_branch_scale(coef, H, W)`): head_bwd sees coef * S_p, input_bwd
+        multiplies by 1 / S_p, so the seed receives its own scale exactly.  `flags` (a list) receives one 0-dim bool tensor per chunk:
+        whether the gradient arriving at the input was finite.  keep_tape=True (tests only; one chunk): -> (values, the 13 forward
+        outputs [2 n, h, w, C], the five d_feats [n, h, w, C] at scale coef * S_p)."""
+        for name, t in (("x", x), ("y", y), ("seed", seed)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 5 or t.shape[1] != 3:
+                raise ValueError(f"LPIPS: {name} must be float32 [B, 3, T, H, W], got {getattr(t, 'dtype', type(t))} "
+                                 f"{tuple(getattr(t, 'shape', ()))}")
+            if t.device != self.device:
+                raise ValueError(f"LPIPS: {name} is on {t.device}, the network on {self.device}")
+        if x.shape != y.shape or seed.shape != y.shape:
+            raise ValueError(f"LPIPS: shapes {tuple(x.shape)}, {tuple(y.shape)} and {tuple(seed.shape)} differ")
+        if not seed.is_contiguous():
+            raise ValueError("LPIPS: seed must be contiguous (it is added into in place)")
+        if self.route != "own":
+            raise RuntimeError("LPIPS.value_and_grad runs on mebt_op_conv2d_3x3 only (MEBT_LPIPS_CONV=own)")
+        x, y = x.contiguous(), y.contiguous()
+        B, _, T, H, W = (int(v) for v in x.shape)
+        if H < MIN_SIZE or W < MIN_SIZE:
+            raise ValueError(f"LPIPS: frames of {H} x {W}: four 2 x 2 pools need H, W >= {MIN_SIZE}")
+        if frames is None:
+            raise ValueError("LPIPS.value_and_grad: `frames` must name one frame per clip or distinct (b, t) pairs")
+        host = self._pairs(frames, B, T)
+        if len({(int(b), int(t)) for b, t in host.tolist()}) != host.shape[0]:
+            raise ValueError("LPIPS.value_and_grad: the (b, t) pairs must be distinct")
+        coef = float(coef)
+        Sp = float(grad_scale) if grad_scale is not None else default_branch_scale(coef, H, W)
+        if not (Sp > 0.0 and math.isfinite(Sp) and math.frexp(Sp)[0] == 0.5):
+            raise ValueError(f"LPIPS.value_and_grad: grad_scale must be a positive power of two, got {grad_scale}")
+        pairs = host.to(self.device)
+        n = int(pairs.shape[0])
+        out = torch.zeros(n, device=self.device, dtype=torch.float64)
+        per = min(n, self.pairs_per_chunk_grad(H, W))
+        if keep_tape and per < n:
+            raise ValueError("LPIPS.value_and_grad: keep_tape needs the pairs to fit one chunk")
+        scratch = torch.empty(max(1, head_scratch_bytes(per, H * W) // 8), device=self.device, dtype=torch.float64)
+        flags = [] if flags is None else flags
+        kept = None
+        for s in range(0, n, per):
+            kept = self._chunk_grad(x, y, pairs[s:s + per], host[s:s + per], out[s:s + per], seed, coef * Sp, 1.0 / Sp, scratch, flags, keep_tape)
+        return (out, kept[0], kept[1]) if keep_tape else out
 
 
 def read_file(path):

@@ -1,9 +1,14 @@
 """`python -m mebt_amd.train_vqgan` — the reconstruction phase of first-stage training: what the reference's `train_vqgan.py` computes
-during its first `--discriminator_iter_start` steps (default 50 000) with `--perceptual_weight 0` (its default), when both GAN terms are
-multiplied by a zero `disc_factor`: the L1 reconstruction loss, the commitment loss, Adam on the autoencoder (vqgan.py:198-206) and
-the EMA codebook with random restarts (modules/codebook.py:34-46,66-89).  Every step is `VQGAN.train_step` on the HIP operators; the
-GAN phase (discriminators) and the LPIPS backward are not built, so `--max_steps` beyond `--discriminator_iter_start` and
-`--perceptual_weight` above 0 end the run with a message before anything is loaded.
+during its first `--discriminator_iter_start` steps (default 50 000), when both GAN terms are multiplied by a zero `disc_factor`: the L1
+reconstruction loss, the commitment loss, with `--perceptual_weight` above 0 the LPIPS term on one drawn frame per clip
+(vqgan.py:104-116; csrc/lpips/lpips_bwd.hip), Adam on the autoencoder (vqgan.py:198-206) and the EMA codebook with random restarts
+(modules/codebook.py:34-46,66-89).  Every step is `VQGAN.train_step` on the HIP operators; the GAN phase (discriminators) is not built, so
+`--max_steps` beyond `--discriminator_iter_start` ends the run with a message before anything is loaded.
+
+`--perceptual_weight` above 0 needs the perceptual weights (13 VGG-16 convolutions + five `lin` layers; nothing here fetches them): from
+`--lpips_ckpt` (any file `mebt_amd.lpips.read_file` takes: a bare state dict or a first-stage checkpoint of the reference), or from the
+`perceptual_model.*` tensors of the checkpoint resumed with `--vqgan_ckpt`.  Without either the run ends with a message.  Checkpoints
+written while the model holds them carry them under `perceptual_model.*`, as the reference's do, so a resume needs no `--lpips_ckpt`.
 
 Flags: the model flags of the reference's `VQGAN.add_model_specific_args`, the data flags of VideoData (`--data_path --image_folder
 --resolution --sequence_length --batch_size --num_workers ...`, as `mebt_amd.measure_recon` takes them; `--data_path` is a frame folder
@@ -58,16 +63,25 @@ def build_parser():
     parser.add_argument('--ckpt_every', type=int, default=5000)
     parser.add_argument('--default_root_dir', type=str, default='vqgan_run')
     parser.add_argument('--vqgan_ckpt', type=str, default='', help='resume from this checkpoint (its hyper-parameters replace the model flags)')
+    parser.add_argument('--lpips_ckpt', type=str, default='', help='the perceptual weights for --perceptual_weight > 0 (a state dict or a '
+                        'reference first-stage checkpoint); not needed when --vqgan_ckpt carries perceptual_model.*')
     parser.add_argument('--dtype', type=str, default='f16', choices=['f16', 'f32'])
     parser.add_argument('--seed', type=int, default=0)
     return parser
 
 
-def check_args(args):
-    """the two phases that are not built end the run here, before data or model are touched"""
+def check_args(args, lpips_available=None):
+    """what cannot run ends here, before data or model are touched.  lpips_available: whether the model holds the perceptual weights;
+    None before anything is loaded, when only the flags can be judged"""
     if args.perceptual_weight > 0.0:
-        raise SystemExit("--perceptual_weight > 0 needs the LPIPS backward, which belongs to the follow-up that completes first-stage training "
-                         "(LPIPS backward, discriminators); set perceptual_weight to 0")
+        ckpt = getattr(args, "lpips_ckpt", "")
+        if ckpt and not os.path.isfile(ckpt):
+            raise SystemExit(f"--lpips_ckpt {ckpt!r}: no such file")
+        if lpips_available is None:
+            lpips_available = bool(ckpt) or bool(getattr(args, "vqgan_ckpt", ""))
+        if not lpips_available:
+            raise SystemExit("--perceptual_weight > 0: the LPIPS backward needs the perceptual weights (13 VGG-16 convolutions, five `lin` layers): pass "
+                             "--lpips_ckpt, or resume a --vqgan_ckpt that carries perceptual_model.* tensors; or set perceptual_weight to 0")
     if args.max_steps > args.discriminator_iter_start:
         raise SystemExit(f"--max_steps {args.max_steps} runs past --discriminator_iter_start {args.discriminator_iter_start}: the GAN phase "
                          "(discriminators, GAN and feature-matching losses) is not built; this command trains the reconstruction phase only")
@@ -79,8 +93,13 @@ def check_args(args):
 
 def checkpoint_dict(model, step):
     """the Lightning layout the reference's `load_from_checkpoint` and this package's `VQGAN.load_from_checkpoint` read"""
-    return {"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "hyper_parameters": {"args": model.args},
-            "global_step": int(step)}
+    sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
+    own = model.lpips_weights
+    if own is not None:                                 # under the reference's keys and shapes: a resume, and the reference, read them
+        from .lpips import PREFIX
+        for k, v in own.items():
+            sd[PREFIX + k] = v.detach().cpu().reshape(1, 3, 1, 1) if k.startswith("scaling_layer.") else v.detach().cpu()
+    return {"state_dict": sd, "hyper_parameters": {"args": model.args}, "global_step": int(step)}
 
 
 def save_checkpoint(model, step, path):
@@ -116,13 +135,18 @@ def main(argv=None):
         ck = torch.load(args.vqgan_ckpt, map_location='cpu', weights_only=False)
         model = VQGAN.load_from_checkpoint(args.vqgan_ckpt)
         step = int(ck.get("global_step", 0))
-        check_args(argparse.Namespace(**{**vars(args), "perceptual_weight": float(model._hp("perceptual_weight", 0.0))}))
         print(f'resumed {args.vqgan_ckpt} at step {step}')
     else:
         hp = argparse.Namespace(**{k: v for k, v in vars(args).items()
                                    if k not in ("max_steps", "log_every", "ckpt_every", "default_root_dir", "vqgan_ckpt", "dtype", "seed")})
         hp.downsample = tuple(hp.downsample)
+        del hp.lpips_ckpt
         model = VQGAN(hp)
+    pw = float(model._hp("perceptual_weight", 0.0))
+    if args.lpips_ckpt and pw > 0.0:
+        from .lpips import read_file
+        model.lpips_weights = read_file(args.lpips_ckpt)
+    check_args(argparse.Namespace(**{**vars(args), "perceptual_weight": pw}), lpips_available=model.lpips_weights is not None)
     model = model.to(device).train()
     model.compute_dtype = args.dtype
     optimizer = model.configure_optimizers()
@@ -133,8 +157,13 @@ def main(argv=None):
         out = model.train_step(next(stream), optimizer, generator=generator)
         step += 1
         if step % args.log_every == 0 or step == args.max_steps:
+            extra = ""
+            if "perceptual_loss" in out:
+                model.log("train/perceptual_loss", out["perceptual_loss"])
+                extra = f" train/perceptual_loss {float(out['perceptual_loss']):.6f}"
             print(f"step {step}: recon_loss {float(out['recon_loss']):.6f} commitment_loss {float(out['commitment_loss']):.6e} "
-                  f"perplexity {float(out['perplexity']):.2f} codes_restarted {int(out['codes_restarted'])} grad_scale {out['grad_scale']:g}", flush=True)
+                  f"perplexity {float(out['perplexity']):.2f} codes_restarted {int(out['codes_restarted'])} grad_scale {out['grad_scale']:g}{extra}",
+                  flush=True)
         if step % args.ckpt_every == 0 and step < args.max_steps:
             print(f"wrote {save_checkpoint(model, step, os.path.join(ckpt_dir, f'step={step}.ckpt'))}")
     print(f"wrote {save_checkpoint(model, step, os.path.join(ckpt_dir, 'last.ckpt'))}")

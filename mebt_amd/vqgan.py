@@ -2,11 +2,11 @@
 operators of csrc/vqgan.hip.  Same constructor argument (`args` namespace with n_hiddens / downsample / image_channels /
 embedding_dim / n_codes), module tree and state-dict names (`encoder.conv_first.conv.weight`, `encoder.conv_blocks.0.res.norm1.weight`,
 `decoder.conv_blocks.0.up.convt.weight`, `pre_vq_conv.conv.weight`, `codebook.embeddings`, ...) so reference checkpoints load;
-the discriminators and the perceptual term's backward are not built (their keys are ignored on load): of
-first-stage training, `recon_backward` gives the gradients of recon_loss + commitment_loss (vqgan.py:98-102,183-184 before
-discriminator_iter_start, perceptual_weight 0) on the kernels of csrc/vqgan_bwd/vqgan_bwd.hip, with the codebook frozen or, with
+the discriminators are not built (their keys are ignored on load): of
+first-stage training, `recon_backward` gives the gradients of recon_loss + commitment_loss + perceptual_loss (vqgan.py:98-116,183-184
+before discriminator_iter_start) on the kernels of csrc/vqgan_bwd/vqgan_bwd.hip and csrc/lpips/lpips_bwd.hip, with the codebook frozen or, with
 `update_codebook=True`, trained by the EMA update with random restarts of modules/codebook.py on csrc/codebook/codebook_train.hip;
-`configure_optimizers` is the reference's autoencoder Adam and `train_step` one step of the two (python -m mebt_amd.train_vqgan); the `perceptual_model.*` tensors are kept for the forward-only LPIPS of mebt_amd/lpips.py.  `validation_step`
+`configure_optimizers` is the reference's autoencoder Adam and `train_step` one step of the two (python -m mebt_amd.train_vqgan); the `perceptual_model.*` tensors are kept for the LPIPS of mebt_amd/lpips.py (forward for validation, `value_and_grad` for the perceptual term).  `validation_step`
 (vqgan.py:190-196) and `reconstruct_stats` report the reconstruction's quality through the metric operators of csrc/recon/recon.hip
 (mebt_amd/recon.py) and, when the checkpoint carried the perceptual weights, csrc/lpips/lpips.hip.
 
@@ -696,10 +696,10 @@ class VQGAN(nn.Module):
         return 2.0 ** math.floor(math.log2(0.125 / c))
 
     def recon_backward(self, x, grad_scale=None, update_codebook=False, restart_src=None, restart_noise=None, init_src=None, init_noise=None,
-                       generator=None):
-        """The autoencoder objective of the reference before `discriminator_iter_start` with `perceptual_weight` 0 (vqgan.py:98-102,183-184):
-        loss = l1_weight * mean |x_recon - x| + 0.25 * mse(z, e.detach()), the codebook frozen, the quantiser straight-through
-        (codebook.py:64,91).  Runs the training forward (`encode` + `decode` recording every convolution's input, every GroupNorm's
+                       generator=None, frame_idx=None):
+        """The autoencoder objective of the reference before `discriminator_iter_start` (vqgan.py:98-116,183-184):
+        loss = l1_weight * mean |x_recon - x| + 0.25 * mse(z, e.detach()) + perceptual_weight * mean_b LPIPS(x[b, :, idx_b],
+        x_recon[b, :, idx_b]), the codebook frozen, the quantiser straight-through (codebook.py:64,91).  Runs the training forward (`encode` + `decode` recording every convolution's input, every GroupNorm's
         input and statistics, z and the ids), then the backward on the operators of csrc/vqgan_bwd/vqgan_bwd.hip, and ADDS the fp32 gradient to
         `.grad` of every parameter of encoder, decoder, pre_vq_conv and post_vq_conv (created where None: autograd's semantics, so
         `optimizer.zero_grad()` works as usual).  The backward is seeded with the power-of-two `grad_scale` S (None:
@@ -708,15 +708,26 @@ class VQGAN(nn.Module):
         -> {recon_loss, commitment_loss, perplexity (0-dim float64 on the device), encodings, grad_scale, finite, x_recon (the
         reconstruction the L1 seed's signs were taken from)}
 
+        perceptual_weight > 0 needs the perceptual weights (`self.lpips`).  `frame_idx` (int [B]; None: drawn after the decode with
+        `torch.randint(0, T, [B])`, as `validation_step` and vqgan.py:104 draw it) names the frame of every clip the term is taken on;
+        `LPIPS.value_and_grad` adds S * perceptual_weight / B * dLPIPS/dx_recon into the L1 seed before `decoder.conv_last`'s backward
+        (csrc/lpips/lpips_bwd.hip).  That branch runs at its own power-of-two scale, `self.perceptual_grad_scale` (None:
+        `lpips.default_branch_scale`); an overflow in it clears `finite`.  The dict gains `perceptual_loss` (0-dim float64) and
+        `frame_idx`.  With perceptual_weight 0 nothing is drawn and the dict is the one above.
+
         update_codebook (default False: the codebook stays frozen, as above) trains the codebook too, as the reference's forward does in
         training mode: while `codebook._need_init` is set, `Codebook.init_from(z)` runs after the encoder and before the arg-min
         (codebook.py:50-51), and `Codebook.update(z, ids)` runs after `mebt_op_vq_seed`, so that the commitment loss, the straight-through
         gradient and the decoder's input all use the codes from BEFORE the update (in the reference `F.embedding` has copied them by
         then).  The dict gains `codes_restarted` (0-dim int32 on the device).  restart_src / restart_noise and init_src / init_noise inject
         the draws of the update and of the initialisation (`Codebook.restart_rows`); `generator` seeds those drawn here."""
-        if float(self._hp("perceptual_weight", 0.0)) > 0.0:
-            raise NotImplementedError("recon_backward: perceptual_weight > 0 needs the LPIPS backward, which belongs to the follow-up that "
-                                      "completes first-stage training (EMA codebook, LPIPS backward, discriminators); set perceptual_weight to 0")
+        pw = float(self._hp("perceptual_weight", 0.0))
+        net = self.lpips if pw > 0.0 else None
+        if pw > 0.0 and net is None:
+            # a RuntimeError, as reconstruct_stats raises for the same lack; of the subclass the earlier refusal of this argument raised,
+            # so that callers who caught that one still do
+            raise NotImplementedError("recon_backward: perceptual_weight > 0 (the LPIPS backward) needs the perceptual weights (a checkpoint "
+                                      "with perceptual_model.* tensors, or `lpips_weights` set from mebt_amd.lpips.read_file)")
         if update_codebook and torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("recon_backward(update_codebook=True) on several ranks needs the all-reduces of n_total and encode_sum and "
                                       "the broadcast of the restart rows (codebook.py:70-72,84-85): data-parallel first-stage training is not built")
@@ -747,6 +758,16 @@ class VQGAN(nn.Module):
         with torch.no_grad():
             seed = torch.empty_like(rec)
             check(lib.mebt_op_l1_seed(ptr(rec), ptr(x), ptr(seed), rec.numel(), S * l1w / rec.numel(), cur_stream()))
+            if net is not None:
+                if frame_idx is None:
+                    frame_idx = torch.randint(0, x.shape[2], [B])
+                keep = bool(self.__dict__.get("_lpips_keep_tape"))          # tests only: the forward outputs the ReLU / pool decisions came from
+                vals = net.value_and_grad(x, rec, frame_idx, seed, S * pw / B, grad_scale=self.__dict__.get("perceptual_grad_scale"),
+                                          keep_tape=keep, flags=flags)
+                if keep:
+                    vals, out["lpips_tape"], _ = vals
+                out["perceptual_loss"] = vals.mean() * pw
+                out["frame_idx"] = torch.as_tensor(frame_idx).detach().to("cpu", torch.int64)
             g = self._conv_bwd("decoder.conv_last", seed, B, tape, inv, flags)
             for i in reversed(range(len(self.decoder.conv_blocks))):
                 blk = self.decoder.conv_blocks[i]
@@ -771,10 +792,10 @@ class VQGAN(nn.Module):
         return out
 
     def train_step(self, x, optimizer, grad_scale=None, **draws):
-        """one step of the reference's recipe before `discriminator_iter_start` with `perceptual_weight` 0: `optimizer.zero_grad()`,
+        """one step of the reference's recipe before `discriminator_iter_start`: `optimizer.zero_grad()`,
         `recon_backward(x, update_codebook=True)`, `optimizer.step()` -> recon_backward's dict.  A non-finite gradient raises before the
         optimizer step (the codebook has been updated by then: it saw only the forward).  `draws`: recon_backward's restart_src /
-        restart_noise / init_src / init_noise / generator."""
+        restart_noise / init_src / init_noise / generator / frame_idx."""
         optimizer.zero_grad()
         out = self.recon_backward(x, grad_scale=grad_scale, update_codebook=True, **draws)
         if not out["finite"]:
