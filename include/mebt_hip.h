@@ -316,6 +316,10 @@ typedef struct mebt_conv3d_desc {
 } mebt_conv3d_desc;
 /* allow_mfma = 0 forces the direct fp32-FMA kernel (the on-GPU reference of the MFMA kernel). */
 int mebt_op_conv3d(int32_t dtype, const mebt_conv3d_desc* d, int32_t allow_mfma, mebt_stream_t stream);
+/* The kernel mebt_op_conv3d runs for this descriptor, as a stable name: "dma_<bm>x<bn>x<ring>" (LDS-DMA implicit GEMM), "mfma_f16"
+ * (register-staged), "first_mfma", "last_mfma_<Cin / 32>", "voxel_<4|32>", "direct"; "none" for an empty class, NULL (error text set)
+ * for what mebt_op_conv3d refuses.  Host only: no GPU call, and only the descriptor's integers and whether `resid` is set are read. */
+const char* mebt_conv3d_route(int32_t dtype, const mebt_conv3d_desc* d, int32_t allow_mfma);
 /* y = silu(GroupNorm_32(x)), eps 1e-6 (vqgan.py:255-258,17-18); stats: scratch [B, 32, 2] fp32. */
 int mebt_op_groupnorm_silu(int32_t dtype, const void* x, void* y, const float* gamma, const float* beta, float* stats, int32_t B,
                            int64_t vox_per_sample, int32_t C, mebt_stream_t stream);

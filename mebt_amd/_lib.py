@@ -76,6 +76,7 @@ PROTOTYPES = {
     "mebt_op_next_mask": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mebt_op_cast_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "mebt_op_conv3d": (c_i32, [c_i32, c_vp, c_i32, c_vp]),
+    "mebt_conv3d_route": (C.c_char_p, [c_i32, c_vp, c_i32]),
     "mebt_op_groupnorm_silu": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "mebt_op_codebook_argmin": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_codebook_argmin_filtered": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),

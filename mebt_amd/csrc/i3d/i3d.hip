@@ -19,9 +19,6 @@
 
 namespace {
 
-typedef _Float16 f16_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int I3D_BK = 32;
 constexpr int I3D_BN = 64;
 constexpr int I3D_MAX_TAB = 2048;      // LDS entries of the K table (8 KiB)

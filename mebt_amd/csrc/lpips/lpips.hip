@@ -24,10 +24,6 @@
 
 namespace {
 
-typedef _Float16 f16_t;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CV_BK = 32, CV_BN = 64, CV_THREADS = 256;
 
 template <typename T> struct CvCfg;

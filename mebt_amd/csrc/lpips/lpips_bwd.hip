@@ -13,8 +13,6 @@
 
 namespace {
 
-typedef _Float16 f16_t;
-
 // ---- head: one wave per pixel, as the forward ------------------------------------------------------------------------------------------
 constexpr int HB_THREADS = 256, HB_WAVES = HB_THREADS / MEBT_WAVE;
 

@@ -16,54 +16,13 @@
 // Cout % 64 == 0), conv3d_direct (any shape / dtype, fp32 FMA: the parity mode, the 3-channel first / last layers and odd
 // channel counts), group-norm statistics + normalise/SiLU, codebook distance arg-min on an exact-fp32 MFMA score matrix,
 // embedding rows.
-#include "common.h"
+#include "conv3d.h"
 #include "kernels.h"
-#include "../../include/mebt_hip.h"
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 namespace {
-
-typedef _Float16 f16_t;
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> __device__ __forceinline__ f32x4 ld4(const T* p);
-template <> __device__ __forceinline__ f32x4 ld4<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-template <> __device__ __forceinline__ f32x4 ld4<f16_t>(const f16_t* p) {
-    const f16x4 v = *reinterpret_cast<const f16x4*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-template <> __device__ __forceinline__ void st4<f16_t>(f16_t* p, f32x4 v) {
-    const f16x4 o = {(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
-    *reinterpret_cast<f16x4*>(p) = o;
-}
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// class-local voxel index -> (b, t', h', w')
-struct Vox { int b, t, h, w; };
-__device__ __forceinline__ Vox decode_vox(const mebt_conv3d_desc& p, long m) {
-    Vox v;
-    v.w = (int)(m % p.cW); m /= p.cW;
-    v.h = (int)(m % p.cH); m /= p.cH;
-    v.t = (int)(m % p.cT); v.b = (int)(m / p.cT);
-    return v;
-}
-// channels-last element offset of the input voxel tap `j` of output voxel v reads (replicate padding = clamp)
-__device__ __forceinline__ size_t in_voxel(const mebt_conv3d_desc& p, const Vox& v, int j) {
-    const int ti = clampi(v.t * p.sm[0] + p.tap[j][0], p.Ti - 1);
-    const int hi = clampi(v.h * p.sm[1] + p.tap[j][1], p.Hi - 1);
-    const int wi = clampi(v.w * p.sm[2] + p.tap[j][2], p.Wi - 1);
-    return (((size_t)v.b * p.Ti + ti) * p.Hi + hi) * p.Wi + wi;
-}
-__device__ __forceinline__ size_t out_voxel(const mebt_conv3d_desc& p, const Vox& v) {
-    const int t = v.t * p.os[0] + p.pi[0], h = v.h * p.os[1] + p.pi[1], w = v.w * p.os[2] + p.pi[2];
-    return (((size_t)v.b * p.To + t) * p.Ho + h) * p.Wo + w;
-}
 
 // ------------------------------------------------------------------------------------------------
 // direct convolution: one thread per (output voxel, output channel), fp32 FMA chain over taps x Cin
@@ -79,18 +38,16 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const mebt_conv3d_de
     const T* wrow = reinterpret_cast<const T*>(p.w) + (size_t)co * p.ntaps * p.Cin;
     for (int j = 0; j < p.ntaps; ++j) {
         if (p.in_mode == 1) {            // fp32 [B, C, T, H, W] (the video)
-            const int ti = clampi(v.t * p.sm[0] + p.tap[j][0], p.Ti - 1);
-            const int hi = clampi(v.h * p.sm[1] + p.tap[j][1], p.Hi - 1);
-            const int wi = clampi(v.w * p.sm[2] + p.tap[j][2], p.Wi - 1);
+            const Coord c = tap_coord(p, v, j);
             const size_t plane = (size_t)p.Ti * p.Hi * p.Wi;
-            const float* x = reinterpret_cast<const float*>(p.in) + (size_t)v.b * p.Cin * plane + ((size_t)ti * p.Hi + hi) * p.Wi + wi;
+            const float* x = reinterpret_cast<const float*>(p.in) + (size_t)v.b * p.Cin * plane + ((size_t)c.t * p.Hi + c.h) * p.Wi + c.w;
             for (int ci = 0; ci < p.Cin; ++ci) acc += x[ci * plane] * (float)wrow[j * p.Cin + ci];
         } else {
             const T* x = reinterpret_cast<const T*>(p.in) + in_voxel(p, v, j) * p.Cin;
             const T* wj = wrow + (size_t)j * p.Cin;
             if ((p.Cin & 3) == 0) {
                 for (int ci = 0; ci < p.Cin; ci += 4) {
-                    const f32x4 a = ld4<T>(x + ci), b = ld4<T>(wj + ci);
+                    const f32x4 a = load4<T>(x + ci), b = load4<T>(wj + ci);
                     acc += a[0] * b[0]; acc += a[1] * b[1]; acc += a[2] * b[2]; acc += a[3] * b[3];
                 }
             } else {
@@ -98,7 +55,7 @@ __global__ __launch_bounds__(256) void conv3d_direct_kernel(const mebt_conv3d_de
             }
         }
     }
-    const size_t ov = out_voxel(p, v);
+    const size_t ov = out_voxel(p, v);      // store_out written out, as it stood: through the call the f32 model runs 0.5 % slower
     if (p.resid) acc += (float)reinterpret_cast<const T*>(p.resid)[ov * p.Cout + co];
     if (p.out_mode == 0) reinterpret_cast<T*>(p.out)[ov * p.Cout + co] = (T)acc;
     else if (p.out_mode == 1) reinterpret_cast<float*>(p.out)[ov * p.Cout + co] = acc;
@@ -135,10 +92,8 @@ __global__ __launch_bounds__(256) void conv3d_voxel_kernel(const mebt_conv3d_des
     for (int c = 0; c < MAXC; ++c) acc[c] = (p.bias && c < p.Cout) ? p.bias[c] : 0.f;
     const size_t plane = (size_t)p.Ti * p.Hi * p.Wi;
     for (int j = 0; j < p.ntaps; ++j) {
-        const int ti = clampi(v.t * p.sm[0] + p.tap[j][0], p.Ti - 1);
-        const int hi = clampi(v.h * p.sm[1] + p.tap[j][1], p.Hi - 1);
-        const int wi = clampi(v.w * p.sm[2] + p.tap[j][2], p.Wi - 1);
-        const size_t sp = ((size_t)ti * p.Hi + hi) * p.Wi + wi;
+        const Coord ci = tap_coord(p, v, j);
+        const size_t sp = ((size_t)ci.t * p.Hi + ci.h) * p.Wi + ci.w;
         const float* wt = wl + (size_t)j * p.Cin * MAXC;
         if (p.in_mode == 1) {                                   // fp32 [B, C, T, H, W]
             const float* x = reinterpret_cast<const float*>(p.in) + (size_t)v.b * p.Cin * plane + sp;
@@ -153,7 +108,7 @@ __global__ __launch_bounds__(256) void conv3d_voxel_kernel(const mebt_conv3d_des
         } else {
             const T* x = reinterpret_cast<const T*>(p.in) + ((size_t)v.b * plane + sp) * p.Cin;
             for (int ci = 0; ci < p.Cin; ci += 4) {             // Cin % 4 == 0 on this path (checked by the launcher)
-                const f32x4 x4 = ld4<T>(x + ci);
+                const f32x4 x4 = load4<T>(x + ci);
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -165,14 +120,8 @@ __global__ __launch_bounds__(256) void conv3d_voxel_kernel(const mebt_conv3d_des
         }
     }
     const size_t ov = out_voxel(p, v);
-    const size_t oplane = (size_t)p.To * p.Ho * p.Wo;
-    for (int c = 0; c < p.Cout; ++c) {
-        float a = acc[c];
-        if (p.resid) a += (float)reinterpret_cast<const T*>(p.resid)[ov * p.Cout + c];
-        if (p.out_mode == 0) reinterpret_cast<T*>(p.out)[ov * p.Cout + c] = (T)a;
-        else if (p.out_mode == 1) reinterpret_cast<float*>(p.out)[ov * p.Cout + c] = a;
-        else reinterpret_cast<float*>(p.out)[((ov / oplane) * p.Cout + c) * oplane + ov % oplane] = a;
-    }
+    const size_t oplane = out_plane(p);
+    for (int c = 0; c < p.Cout; ++c) store_out<T>(p, ov, c, acc[c], oplane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -223,6 +172,7 @@ __global__ __launch_bounds__(256) void conv3d_first_mfma_kernel(const mebt_conv3
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const uint32_t c = tk[ks][j];
+                // tap_coord with this lane's taps unpacked from tk (the voxel's part, t0 / h0 / w0, is hoisted out of the k loop)
                 const int ti = clampi(t0 + (int)(c & 255u), p.Ti - 1);
                 const int hi = clampi(h0 + (int)((c >> 8) & 255u), p.Hi - 1);
                 const int wi = clampi(w0 + (int)((c >> 16) & 255u), p.Wi - 1);
@@ -239,7 +189,7 @@ __global__ __launch_bounds__(256) void conv3d_first_mfma_kernel(const mebt_conv3
             const int n = 16 * cf + 4 * g;
             f32x4 o = acc[cf];
             if (p.bias) o += *reinterpret_cast<const f32x4*>(p.bias + n);
-            st4<f16_t>(reinterpret_cast<f16_t*>(p.out) + ov * p.Cout + n, o);
+            store4<f16_t>(reinterpret_cast<f16_t*>(p.out) + ov * p.Cout + n, o);
         }
     }
 }
@@ -285,10 +235,8 @@ __global__ __launch_bounds__(256) void conv3d_last_mfma_kernel(const mebt_conv3d
         auto load_tap = [&](int j, int buf) {
 #pragma unroll
             for (int i = 0; i < RF; ++i) {
-                const int ti = clampi(v[i].t * p.sm[0] + p.tap[j][0], p.Ti - 1);
-                const int hi = clampi(v[i].h * p.sm[1] + p.tap[j][1], p.Hi - 1);
-                const int wi = clampi(v[i].w * p.sm[2] + p.tap[j][2], p.Wi - 1);
-                const uint32_t vox = (uint32_t)(((v[i].b * p.Ti + ti) * p.Hi + hi) * p.Wi + wi);      // < 2^31 input elements (launcher)
+                const Coord ci = tap_coord(p, v[i], j);
+                const uint32_t vox = (uint32_t)(((v[i].b * p.Ti + ci.t) * p.Hi + ci.h) * p.Wi + ci.w);      // < 2^31 input elements (launcher)
                 const f16_t* src = in + vox * (uint32_t)p.Cin + 8 * g;
 #pragma unroll
                 for (int c = 0; c < KC2; ++c)
@@ -315,7 +263,7 @@ __global__ __launch_bounds__(256) void conv3d_last_mfma_kernel(const mebt_conv3d
                     for (int i = 0; i < RF; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, af[1][c][i], acc[i], 0, 0, 0);
                 }
         }
-        const size_t oplane = (size_t)p.To * p.Ho * p.Wo;
+        const size_t oplane = out_plane(p);
 #pragma unroll
         for (int i = 0; i < RF; ++i) {
             if (!live[i]) continue;
@@ -323,12 +271,7 @@ __global__ __launch_bounds__(256) void conv3d_last_mfma_kernel(const mebt_conv3d
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int c = 4 * g + q;
-                if (c >= p.Cout) continue;
-                float a = acc[i][q] + (p.bias ? p.bias[c] : 0.f);
-                if (p.resid) a += (float)reinterpret_cast<const f16_t*>(p.resid)[ov * p.Cout + c];
-                if (p.out_mode == 0) reinterpret_cast<f16_t*>(p.out)[ov * p.Cout + c] = (f16_t)a;
-                else if (p.out_mode == 1) reinterpret_cast<float*>(p.out)[ov * p.Cout + c] = a;
-                else reinterpret_cast<float*>(p.out)[((ov / oplane) * p.Cout + c) * oplane + ov % oplane] = a;
+                if (c < p.Cout) store_out<f16_t>(p, ov, c, acc[i][q] + (p.bias ? p.bias[c] : 0.f), oplane);
             }
         }
     }
@@ -417,9 +360,9 @@ __global__ __launch_bounds__(256) void conv3d_mfma_f16_kernel(const mebt_conv3d_
             const int n = n0 + 16 * j + 4 * (lane >> 4);
             f32x4 v = acc[i][j];
             if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + n);
-            if (p.resid) v += ld4<f16_t>(reinterpret_cast<const f16_t*>(p.resid) + ov * p.Cout + n);
+            if (p.resid) v += load4<f16_t>(reinterpret_cast<const f16_t*>(p.resid) + ov * p.Cout + n);
             if (p.out_mode == 1) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + ov * p.Cout + n) = v;
-            else st4<f16_t>(reinterpret_cast<f16_t*>(p.out) + ov * p.Cout + n, v);
+            else store4<f16_t>(reinterpret_cast<f16_t*>(p.out) + ov * p.Cout + n, v);
         }
     }
 }
@@ -584,7 +527,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* x, float* stats,
     f32x4 s = {0, 0, 0, 0}, q = {0, 0, 0, 0};
     if (rl < rows_par)
         for (long r = r0 + rl; r < r1; r += rows_par) {
-            const f32x4 v = ld4<T>(x + ((size_t)b * vox_per_sample + r) * C + cl * 4);
+            const f32x4 v = load4<T>(x + ((size_t)b * vox_per_sample + r) * C + cl * 4);
             s += v; q += v * v;
         }
 #pragma unroll
@@ -616,19 +559,18 @@ __global__ __launch_bounds__(256) void gn_apply_silu_kernel(const T* x, T* y, co
         const long e = i * 4;
         const int c = (int)(e % C);
         const long b = e / ((long)vox_per_sample * C);
-        const f32x4 v = ld4<T>(x + e);
+        const f32x4 v = load4<T>(x + e);
         const f32x4 g4 = *reinterpret_cast<const f32x4*>(gamma + c), b4 = *reinterpret_cast<const f32x4*>(beta + c);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int g = (c + j) / cpg;
-            const float sum = stats[((size_t)b * 32 + g) * 2], sq = stats[((size_t)b * 32 + g) * 2 + 1];
-            const float mean = sum * inv_n;
-            const float var = fmaxf(sq * inv_n - mean * mean, 0.f);
-            const float h = (v[j] - mean) * rsqrtf(var + 1e-6f) * g4[j] + b4[j];
+            float mean, rstd;
+            gn_mean_rstd(stats[((size_t)b * 32 + g) * 2], stats[((size_t)b * 32 + g) * 2 + 1], inv_n, mean, rstd);
+            const float h = (v[j] - mean) * rstd * g4[j] + b4[j];
             o[j] = h / (1.0f + __expf(-h));
         }
-        st4<T>(y + e, o);
+        store4<T>(y + e, o);
     }
 }
 
@@ -806,93 +748,128 @@ __global__ __launch_bounds__(256) void embedding_rows_kernel(const int64_t* ids,
         const int c = (int)(i % d4) * 4;
         long id = ids[r];
         id = id < 0 ? 0 : (id >= n_codes ? n_codes - 1 : id);
-        st4<T>(out + (size_t)r * d + c, *reinterpret_cast<const f32x4*>(e + (size_t)id * d + c));
+        store4<T>(out + (size_t)r * d + c, *reinterpret_cast<const f32x4*>(e + (size_t)id * d + c));
     }
 }
 
 template <typename TS, typename TD>
 __global__ __launch_bounds__(256) void cast_kernel(const TS* src, TD* dst, size_t n) {
-    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 1024) st4<TD>(dst + i, ld4<TS>(src + i));
+    for (size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * 1024) store4<TD>(dst + i, load4<TS>(src + i));
 }
 
 }  // namespace
 
-static hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-static bool is_f16(int dtype) { return dtype == MEBT_DTYPE_F16; }
+// Which kernel a convolution gets.  conv3d_route decides from the descriptor's integers alone (no GPU call, no data pointer read);
+// mebt_op_conv3d launches what it names; mebt_conv3d_route tells a caller (tests/test_vqgan_route_host.py) the name.
+typedef void (*conv_kernel_t)(const mebt_conv3d_desc);
+struct DmaTile { int bm, bn, ring; conv_kernel_t fn; const char* name; };
+#define DMA_TILE(BM_, BN_, ST_) {BM_, BN_, ST_, conv3d_mfma_f16_dma_kernel<BM_, BN_, ST_>, "dma_" #BM_ "x" #BN_ "x" #ST_}
+static const DmaTile DMA_TILES[] = {DMA_TILE(128, 128, 2), DMA_TILE(128, 128, 3), DMA_TILE(128, 64, 2), DMA_TILE(128, 64, 3),
+                                    DMA_TILE(256, 64, 2),  DMA_TILE(256, 64, 3),  DMA_TILE(256, 128, 2)};
+#undef DMA_TILE
+struct LastMfma { int kc2; conv_kernel_t fn; const char* name; };            // kc2 = Cin / 32
+static const LastMfma LAST_MFMA[] = {{1, conv3d_last_mfma_kernel<1>, "last_mfma_1"}, {2, conv3d_last_mfma_kernel<2>, "last_mfma_2"},
+                                     {4, conv3d_last_mfma_kernel<4>, "last_mfma_4"}};
+constexpr size_t LAST_MFMA_LDS = 96 * 1024;
+
+// MEBT_CONV_TILE=bm,bn,ring asks for a tile of the table.  What it gets otherwise is what the if-chain this table replaced gave: a
+// ring depth that is not built runs the same tile's ring-3 kernel, a tile that is not built runs 256 x 128 x 2.  Unlike that chain,
+// which kept the grid of the tile asked for, the launch takes the grid of the kernel that runs (conv3d_route drops a width Cout cannot take).
+static const DmaTile& dma_tile(int bm, int bn, int ring) {
+    const DmaTile* deeper = nullptr;
+    for (const DmaTile& t : DMA_TILES) {
+        if (t.bm == bm && t.bn == bn && t.ring == ring) return t;
+        if (t.bm == bm && t.bn == bn && t.ring == 3) deeper = &t;
+    }
+    return deeper ? *deeper : DMA_TILES[6];
+}
+
+// the three environment knobs (conv3d_route reads them once per process)
+struct ConvKnobs { int dma, thin_mfma, tile[3]; };
+static ConvKnobs conv_knobs() {
+    ConvKnobs k = {1, 1, {0, 0, 0}};
+    if (const char* e = getenv("MEBT_CONV_DMA")) k.dma = e[0] != '0';                 // 0: the first (register-staged) kernel
+    if (const char* e = getenv("MEBT_CONV_THIN_MFMA")) k.thin_mfma = e[0] != '0';     // 0: the 3-channel boundary layers on the vector ALUs
+    if (const char* e = getenv("MEBT_CONV_TILE")) sscanf(e, "%d,%d,%d", &k.tile[0], &k.tile[1], &k.tile[2]);     // experiments
+    return k;
+}
+
+enum ConvFamily { CONV_DMA, CONV_MFMA, CONV_FIRST_MFMA, CONV_LAST_MFMA, CONV_VOXEL, CONV_DIRECT };
+struct ConvRoute {
+    ConvFamily family; const char* name; conv_kernel_t fn;
+    int bm, bn, ring;       // CONV_DMA: the row of DMA_TILES
+    int width;              // CONV_LAST_MFMA: KC2 = Cin / 32; CONV_VOXEL: MAXC, the output channels held per thread (4 or 32)
+};
+
+static ConvRoute conv3d_route(int dtype, const mebt_conv3d_desc& p, int allow_mfma) {
+    static const ConvKnobs k = conv_knobs();
+    const bool f16 = is_f16(dtype);
+    const size_t in_elems = (size_t)p.B * p.Ti * p.Hi * p.Wi * p.Cin;
+    const bool mfma = allow_mfma && f16 && p.in_mode == 0 && p.out_mode != 2 && p.Cin % CBK == 0 && p.Cout % CBN == 0;
+    if (mfma && k.dma && p.Cin % 64 == 0 && p.Cout % 64 == 0 && in_elems * 2 < (1ull << 32)) {       // 32-bit byte offsets into the input
+        // tile: 128 x 128 (two workgroups per CU at ring depth 2) where Cout allows, else 256 x 64
+        const DmaTile& own = p.Cout % 128 == 0 ? DMA_TILES[0] : DMA_TILES[4];
+        const DmaTile& forced = k.tile[0] && k.tile[1] > 0 && p.Cout % k.tile[1] == 0 ? dma_tile(k.tile[0], k.tile[1], k.tile[2]) : own;
+        const DmaTile& t = p.Cout % forced.bn == 0 ? forced : own;          // the grid is the launched kernel's: its width must divide Cout too
+        return {CONV_DMA, t.name, t.fn, t.bm, t.bn, t.ring};
+    }
+    if (mfma) return {CONV_MFMA, "mfma_f16", conv3d_mfma_f16_kernel};
+    const bool thin = allow_mfma && k.thin_mfma && f16 && in_elems < (1ull << 31);      // the thin MFMA kernels index the input with 32 bits
+    // the TATS first layer: 3 -> 32 channels from the NCDHW video, 27 taps (K = 81 in three k-steps, two column fragments)
+    if (thin && p.in_mode == 1 && p.Cin == 3 && p.out_mode == 0 && !p.resid && p.Cout == 32 && p.ntaps * 3 > 64 && p.ntaps * 3 <= 96)
+        return {CONV_FIRST_MFMA, "first_mfma", conv3d_first_mfma_kernel<3, 3, 2>};
+    if (thin && p.in_mode == 0 && p.Cout <= 16 && (size_t)p.ntaps * (p.Cin / 32) * 1024 <= LAST_MFMA_LDS)
+        for (const LastMfma& l : LAST_MFMA)
+            if (p.Cin == 32 * l.kc2) return {CONV_LAST_MFMA, l.name, l.fn, 0, 0, 0, l.kc2};
+    // thin layers on the vector ALUs: Cout <= 4 with Cin % 4 == 0 or NCDHW input, or NCDHW input with Cout <= 32; the weights fit 64 KB of LDS
+    const int maxc = p.Cout <= 4 ? 4 : (p.Cout <= 32 && p.in_mode == 1 ? 32 : 0);
+    if (allow_mfma && maxc && (p.in_mode == 1 || p.Cin % 4 == 0) && (size_t)p.ntaps * p.Cin * maxc * 4 <= 64 * 1024)
+        return maxc == 4 ? ConvRoute{CONV_VOXEL, "voxel_4", f16 ? conv3d_voxel_kernel<f16_t, 4> : conv3d_voxel_kernel<float, 4>, 0, 0, 0, 4}
+                         : ConvRoute{CONV_VOXEL, "voxel_32", f16 ? conv3d_voxel_kernel<f16_t, 32> : conv3d_voxel_kernel<float, 32>, 0, 0, 0, 32};
+    return {CONV_DIRECT, "direct", f16 ? conv3d_direct_kernel<f16_t> : conv3d_direct_kernel<float>};
+}
+
+// what both entry points check before they look at the geometry; 0 or a status with the error text set
+static int conv3d_check(int32_t dtype, const mebt_conv3d_desc* d) {
+    if (!d) { mebt_set_error("conv3d: null pointer"); return MEBT_EINVAL; }
+    if (!dtype_ok(dtype)) { mebt_set_error("conv3d: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (d->ntaps < 1 || d->ntaps > MEBT_CONV_MAX_TAPS || d->Cin < 1 || d->Cout < 1) { mebt_set_error("conv3d: bad tap / channel count"); return MEBT_ESHAPE; }
+    return MEBT_OK;
+}
+
+extern "C" const char* mebt_conv3d_route(int32_t dtype, const mebt_conv3d_desc* d, int32_t allow_mfma) {
+    if (conv3d_check(dtype, d)) return nullptr;
+    return (long)d->B * d->cT * d->cH * d->cW <= 0 ? "none" : conv3d_route(dtype, *d, allow_mfma).name;
+}
 
 extern "C" int mebt_op_conv3d(int32_t dtype, const mebt_conv3d_desc* d, int32_t allow_mfma, mebt_stream_t stream) {
-    if (!d || !d->in || !d->out || !d->w) { mebt_set_error("conv3d: null pointer"); return MEBT_EINVAL; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("conv3d: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (d && (!d->in || !d->out || !d->w)) { mebt_set_error("conv3d: null pointer"); return MEBT_EINVAL; }
+    if (int rc = conv3d_check(dtype, d)) return rc;
     const mebt_conv3d_desc& p = *d;
-    if (p.ntaps < 1 || p.ntaps > MEBT_CONV_MAX_TAPS || p.Cin < 1 || p.Cout < 1) { mebt_set_error("conv3d: bad tap / channel count"); return MEBT_ESHAPE; }
     const long mcls = (long)p.B * p.cT * p.cH * p.cW;
     if (mcls <= 0) return MEBT_OK;
-    const bool mfma = allow_mfma && is_f16(dtype) && p.in_mode == 0 && p.out_mode != 2 && p.Cin % CBK == 0 && p.Cout % CBN == 0;
-    // thin layers (video boundary): Cout <= 4 with any Cin % 4 == 0 / NCDHW input, or NCDHW input with Cout <= 32
-    const bool chan_ok = p.in_mode == 1 || p.Cin % 4 == 0;
-    const int maxc = p.Cout <= 4 ? 4 : (p.Cout <= 32 && p.in_mode == 1 ? 32 : 0);
-    const size_t vlds = (size_t)p.ntaps * p.Cin * maxc * 4;
-    static const int conv_dma = [] { const char* e = getenv("MEBT_CONV_DMA"); return (e && e[0] == '0') ? 0 : 1; }();   // 0: the first (register-staged) kernel
-    const bool small_in = (size_t)p.B * p.Ti * p.Hi * p.Wi * p.Cin < (1ull << 31);      // the thin MFMA kernels index the input with 32 bits
-    static const int thin_mfma = [] { const char* e = getenv("MEBT_CONV_THIN_MFMA"); return (e && e[0] == '0') ? 0 : 1; }();   // 0: the 3-channel boundary layers on the vector ALUs (conv3d_voxel_kernel)
-    if (mfma && conv_dma && p.Cin % 64 == 0 && p.Cout % 64 == 0 && (size_t)p.B * p.Ti * p.Hi * p.Wi * p.Cin * 2 < (1ull << 32)) {
-        // tile: 128 x 128 (two workgroups per CU at ring depth 2) where Cout allows, else 256 x 64; MEBT_CONV_TILE=bm,bn,ring (experiments)
-        static int force[3] = {0, 0, 0};
-        static const int attrs = [] {
-#define CONV_ATTR(BM_, BN_, ST_) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_mfma_f16_dma_kernel<BM_, BN_, ST_>), hipFuncAttributeMaxDynamicSharedMemorySize, ST_ * (BM_ + BN_) * 128)
-            CONV_ATTR(128, 128, 2); CONV_ATTR(128, 128, 3); CONV_ATTR(128, 64, 2); CONV_ATTR(128, 64, 3); CONV_ATTR(256, 64, 2); CONV_ATTR(256, 64, 3);
-            CONV_ATTR(256, 128, 2);
-#undef CONV_ATTR
-            if (const char* e = getenv("MEBT_CONV_TILE")) sscanf(e, "%d,%d,%d", &force[0], &force[1], &force[2]);
-            return 0;
-        }();
-        (void)attrs;
-        int bm = p.Cout % 128 == 0 ? 128 : 256, bn = p.Cout % 128 == 0 ? 128 : 64, ring = 2;
-        if (force[0] && p.Cout % force[1] == 0) { bm = force[0]; bn = force[1]; ring = force[2]; }
-        const dim3 grid((unsigned)((mcls + bm - 1) / bm), p.Cout / bn);
-#define CONV_GO(BM_, BN_, ST_) hipLaunchKernelGGL((conv3d_mfma_f16_dma_kernel<BM_, BN_, ST_>), grid, dim3(256), ST_ * (BM_ + BN_) * 128, S(stream), p)
-        if (bm == 128 && bn == 128 && ring == 2) CONV_GO(128, 128, 2);
-        else if (bm == 128 && bn == 128) CONV_GO(128, 128, 3);
-        else if (bm == 128 && bn == 64 && ring == 2) CONV_GO(128, 64, 2);
-        else if (bm == 128 && bn == 64) CONV_GO(128, 64, 3);
-        else if (bm == 256 && bn == 64 && ring == 2) CONV_GO(256, 64, 2);
-        else if (bm == 256 && bn == 64) CONV_GO(256, 64, 3);
-        else CONV_GO(256, 128, 2);
-#undef CONV_GO
-    } else if (mfma) {
-        const dim3 grid((unsigned)((mcls + CBM - 1) / CBM), p.Cout / CBN);
-        hipLaunchKernelGGL(conv3d_mfma_f16_kernel, grid, dim3(256), 0, S(stream), p);
-    } else if (allow_mfma && thin_mfma && small_in && is_f16(dtype) && p.in_mode == 1 && p.Cin == 3 && p.out_mode == 0 && !p.resid && p.Cout == 32 && p.ntaps * 3 > 64 &&
-               p.ntaps * 3 <= 96) {          // the TATS first layer: 3 -> 32 channels, 27 taps (K = 81 in three k-steps, two column fragments)
-        const long nblk = (mcls + 15) / 16;
-        const unsigned wgs = (unsigned)((nblk + 3) / 4 < 2048 ? (nblk + 3) / 4 : 2048);
-        hipLaunchKernelGGL((conv3d_first_mfma_kernel<3, 3, 2>), dim3(wgs), dim3(256), 0, S(stream), p);
-    } else if (allow_mfma && thin_mfma && small_in && is_f16(dtype) && p.in_mode == 0 && (p.Cin == 32 || p.Cin == 64 || p.Cin == 128) && p.Cout <= 16 && (size_t)p.ntaps * (p.Cin / 32) * 1024 <= 96 * 1024) {
-        const size_t lds = (size_t)p.ntaps * (p.Cin / 32) * 1024;
-        static bool attr = false;
-        if (!attr) {
-            MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_last_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_last_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            MEBT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_last_mfma_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr = true;
-        }
-        const long nblk = (mcls + 63) / 64;
-        const unsigned wgs = (unsigned)((nblk + 3) / 4 < 1024 ? (nblk + 3) / 4 : 1024);
-        if (p.Cin == 32) hipLaunchKernelGGL(conv3d_last_mfma_kernel<1>, dim3(wgs), dim3(256), lds, S(stream), p);
-        else if (p.Cin == 64) hipLaunchKernelGGL(conv3d_last_mfma_kernel<2>, dim3(wgs), dim3(256), lds, S(stream), p);
-        else hipLaunchKernelGGL(conv3d_last_mfma_kernel<4>, dim3(wgs), dim3(256), lds, S(stream), p);
-    } else if (allow_mfma && maxc && chan_ok && vlds <= 64 * 1024) {
-        const dim3 grid((unsigned)((mcls + 255) / 256));
-#define VOX(T_, C_) hipLaunchKernelGGL((conv3d_voxel_kernel<T_, C_>), grid, dim3(256), vlds, S(stream), p)
-        if (is_f16(dtype)) { if (maxc == 4) VOX(f16_t, 4); else VOX(f16_t, 32); }
-        else { if (maxc == 4) VOX(float, 4); else VOX(float, 32); }
-#undef VOX
-    } else {
-        const long total = mcls * p.Cout;
-        const dim3 grid((unsigned)((total + 255) / 256));
-        if (is_f16(dtype)) hipLaunchKernelGGL(conv3d_direct_kernel<f16_t>, grid, dim3(256), 0, S(stream), p);
-        else hipLaunchKernelGGL(conv3d_direct_kernel<float>, grid, dim3(256), 0, S(stream), p);
+    static const hipError_t last_attrs = [] {        // dynamic LDS above the default limit, once, from the two tables
+        hipError_t e = hipSuccess;
+        for (const DmaTile& t : DMA_TILES)          // a failure here shows at the launch, as it always did
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(t.fn), hipFuncAttributeMaxDynamicSharedMemorySize, t.ring * (t.bm + t.bn) * 128);
+        for (const LastMfma& l : LAST_MFMA)
+            if (hipError_t x = hipFuncSetAttribute(reinterpret_cast<const void*>(l.fn), hipFuncAttributeMaxDynamicSharedMemorySize, LAST_MFMA_LDS)) e = x;
+        return e;
+    }();
+    const ConvRoute r = conv3d_route(dtype, p, allow_mfma);
+    if (r.family == CONV_LAST_MFMA) MEBT_HIP_CHECK(last_attrs);
+    auto blocks = [](long n, long per, long cap) { const long b = (n + per - 1) / per; return (unsigned)(b < cap ? b : cap); };
+    dim3 grid(blocks(mcls, 256, 1l << 31));          // CONV_VOXEL: a thread per voxel
+    size_t lds = 0;
+    switch (r.family) {
+    case CONV_DMA: grid = dim3(blocks(mcls, r.bm, 1l << 31), p.Cout / r.bn); lds = r.ring * (r.bm + r.bn) * 128; break;
+    case CONV_MFMA: grid = dim3(blocks(mcls, CBM, 1l << 31), p.Cout / CBN); break;
+    case CONV_FIRST_MFMA: grid = dim3(blocks(mcls, 16 * 4, 2048)); break;                 // a wave per 16-voxel row block, grid stride
+    case CONV_LAST_MFMA: grid = dim3(blocks(mcls, 64 * 4, 1024)); lds = (size_t)p.ntaps * r.width * 1024; break;       // a wave per 64 voxels
+    case CONV_VOXEL: lds = (size_t)p.ntaps * p.Cin * r.width * 4; break;
+    case CONV_DIRECT: grid = dim3(blocks(mcls * p.Cout, 256, 1l << 31)); break;           // a thread per (voxel, channel)
     }
+    hipLaunchKernelGGL(r.fn, grid, dim3(256), lds, S(stream), p);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -901,21 +878,18 @@ extern "C" int mebt_op_groupnorm_silu(int32_t dtype, const void* x, void* y, con
                                       int32_t B, int64_t vox_per_sample, int32_t C, mebt_stream_t stream) {
     if (!x || !y || !gamma || !beta || !stats) { mebt_set_error("groupnorm: null pointer"); return MEBT_EINVAL; }
     if (C % 32 || C > 1024 || (C / 4) > 256) { mebt_set_error("groupnorm: channels must be a multiple of 32 (32 groups) and <= 1024"); return MEBT_ESHAPE; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("groupnorm: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (!dtype_ok(dtype)) { mebt_set_error("groupnorm: dtype must be f32 or f16"); return MEBT_EDTYPE; }
     if (B <= 0 || vox_per_sample <= 0) return MEBT_OK;
     MEBT_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * 32 * 2 * 4, S(stream)));
-    int rpb = 64;
-    while ((vox_per_sample + rpb - 1) / rpb > 512) rpb *= 2;               // <= 512 adders per statistic
+    const int rpb = gn_rows_per_block(vox_per_sample);
     const dim3 grid((unsigned)((vox_per_sample + rpb - 1) / rpb), B);
     const long total4 = (long)B * vox_per_sample * C / 4;
-    const unsigned ablocks = (unsigned)((total4 + 255) / 256 < 8192 ? (total4 + 255) / 256 : 8192);
-    if (is_f16(dtype)) {
-        hipLaunchKernelGGL(gn_stats_kernel<f16_t>, grid, dim3(256), 0, S(stream), (const f16_t*)x, stats, (long)vox_per_sample, C, rpb);
-        hipLaunchKernelGGL(gn_apply_silu_kernel<f16_t>, dim3(ablocks), dim3(256), 0, S(stream), (const f16_t*)x, (f16_t*)y, stats, gamma, beta, (long)vox_per_sample, C, total4);
-    } else {
-        hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(256), 0, S(stream), (const float*)x, stats, (long)vox_per_sample, C, rpb);
-        hipLaunchKernelGGL(gn_apply_silu_kernel<float>, dim3(ablocks), dim3(256), 0, S(stream), (const float*)x, (float*)y, stats, gamma, beta, (long)vox_per_sample, C, total4);
-    }
+    const unsigned ablocks = blocks_for((size_t)total4, 8192);
+    auto run = [&](auto* xt, auto* yt) {
+        hipLaunchKernelGGL(gn_stats_kernel, grid, dim3(256), 0, S(stream), xt, stats, (long)vox_per_sample, C, rpb);
+        hipLaunchKernelGGL(gn_apply_silu_kernel, dim3(ablocks), dim3(256), 0, S(stream), xt, yt, stats, gamma, beta, (long)vox_per_sample, C, total4);
+    };
+    if (is_f16(dtype)) run((const f16_t*)x, (f16_t*)y); else run((const float*)x, (float*)y);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -971,8 +945,7 @@ extern "C" int mebt_op_embedding_rows(int32_t dtype, const int64_t* ids, const f
     if (!ids || !embeddings || !out) { mebt_set_error("embedding_rows: null pointer"); return MEBT_EINVAL; }
     if (d % 4) { mebt_set_error("embedding_rows: d must be a multiple of 4"); return MEBT_ESHAPE; }
     if (rows <= 0) return MEBT_OK;
-    const long n4 = rows * (d / 4);
-    const unsigned blocks = (unsigned)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+    const unsigned blocks = blocks_for((size_t)rows * (d / 4), 8192);
     if (is_f16(dtype)) hipLaunchKernelGGL(embedding_rows_kernel<f16_t>, dim3(blocks), dim3(256), 0, S(stream), ids, embeddings, (f16_t*)out, (long)rows, d, n_codes);
     else if (dtype == MEBT_DTYPE_F32) hipLaunchKernelGGL(embedding_rows_kernel<float>, dim3(blocks), dim3(256), 0, S(stream), ids, embeddings, (float*)out, (long)rows, d, n_codes);
     else { mebt_set_error("embedding_rows: dtype must be f32 or f16"); return MEBT_EDTYPE; }
@@ -984,8 +957,7 @@ extern "C" int mebt_op_embedding_rows(int32_t dtype, const int64_t* ids, const f
 extern "C" int mebt_op_cast_f16(const float* src, void* dst, int64_t n, mebt_stream_t stream) {
     if (!src || !dst || n < 0 || (n % 4)) { mebt_set_error("cast_f16: bad arguments"); return MEBT_EINVAL; }
     if (!n) return MEBT_OK;
-    const size_t blocks = ((size_t)n / 4 + 255) / 256;
-    hipLaunchKernelGGL((cast_kernel<float, f16_t>), dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, S(stream), src, (f16_t*)dst, (size_t)n);
+    hipLaunchKernelGGL((cast_kernel<float, f16_t>), dim3(blocks_for((size_t)n / 4, 4096)), dim3(256), 0, S(stream), src, (f16_t*)dst, (size_t)n);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

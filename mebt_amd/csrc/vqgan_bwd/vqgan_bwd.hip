@@ -14,26 +14,10 @@
 //   GroupNorm + SiLU                 h and sigmoid(h) recomputed from x and the forward's statistics; per-channel slabs, fixed-order
 //                                    fp64 finish, then dx.
 //   seeds                            L1 sign seed, quantiser seed (commitment + straight-through).
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+#include "../conv3d.h"
 #include <string.h>
 
 namespace {
-
-typedef _Float16 f16_t;
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-struct Vox { int b, t, h, w; };
-__device__ __forceinline__ Vox decode_vox(const mebt_conv3d_desc& p, long m) {
-    Vox v;
-    v.w = (int)(m % p.cW); m /= p.cW;
-    v.h = (int)(m % p.cH); m /= p.cH;
-    v.t = (int)(m % p.cT); v.b = (int)(m / p.cT);
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------
 // zero-padded copy: dst [B, pT, pH, pW, C] of T <- src at offset `front`, zero elsewhere
@@ -94,25 +78,31 @@ __global__ __launch_bounds__(256) void halo_fold_kernel(const float* dxp, const 
 // ------------------------------------------------------------------------------------------------
 constexpr int WT = 64, WK = 32, WLD = 40;
 
+// channels c0 .. c0 + 7 of one channels-last voxel (C channels at s): 16-byte loads where C % 8 == 0, else scalars; channels >= C keep a's value
+template <typename T>
+__device__ __forceinline__ void load8_cl(const T* s, int c0, int C, T (&a)[8]) {
+    if ((C & 7) == 0) {
+        if (c0 < C) {
+            *reinterpret_cast<u32x4*>(a) = *reinterpret_cast<const u32x4*>(s + c0);
+            if (sizeof(T) == 4) *reinterpret_cast<u32x4*>(a + 4) = *reinterpret_cast<const u32x4*>(s + c0 + 4);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) if (c0 + q < C) a[q] = s[c0 + q];
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ void load8_dy(const mebt_conv3d_desc& p, size_t ov, int c0, T (&a)[8]) {
     if (p.out_mode == 0) {
-        const T* s = reinterpret_cast<const T*>(p.out) + ov * p.Cout;
-        if ((p.Cout & 7) == 0) {
-            if (c0 < p.Cout) {
-                if (sizeof(T) == 2) *reinterpret_cast<u32x4*>(a) = *reinterpret_cast<const u32x4*>(s + c0);
-                else { *reinterpret_cast<u32x4*>(a) = *reinterpret_cast<const u32x4*>(s + c0); *reinterpret_cast<u32x4*>(a + 4) = *reinterpret_cast<const u32x4*>(s + c0 + 4); }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) if (c0 + q < p.Cout) a[q] = s[c0 + q];
-        }
+        const T* s = reinterpret_cast<const T*>(p.out) + out_cl(p, ov, 0);
+        load8_cl(s, c0, p.Cout, a);
     } else if (p.out_mode == 1) {
-        const float* s = reinterpret_cast<const float*>(p.out) + ov * p.Cout;
+        const float* s = reinterpret_cast<const float*>(p.out) + out_cl(p, ov, 0);
 #pragma unroll
         for (int q = 0; q < 8; ++q) if (c0 + q < p.Cout) a[q] = (T)s[c0 + q];
     } else {
-        const size_t plane = (size_t)p.To * p.Ho * p.Wo;
+        const size_t plane = out_plane(p);            // out_ncdhw(p, ov, c0 + q, plane) with the sample's base taken once
         const float* s = reinterpret_cast<const float*>(p.out) + (ov / plane) * p.Cout * plane + ov % plane;
 #pragma unroll
         for (int q = 0; q < 8; ++q) if (c0 + q < p.Cout) a[q] = (T)s[(size_t)(c0 + q) * plane];
@@ -121,21 +111,11 @@ __device__ __forceinline__ void load8_dy(const mebt_conv3d_desc& p, size_t ov, i
 
 template <typename T>
 __device__ __forceinline__ void load8_x(const mebt_conv3d_desc& p, const Vox& v, int j, int c0, T (&b)[8]) {
-    const int ti = clampi(v.t * p.sm[0] + p.tap[j][0], p.Ti - 1);
-    const int hi = clampi(v.h * p.sm[1] + p.tap[j][1], p.Hi - 1);
-    const int wi = clampi(v.w * p.sm[2] + p.tap[j][2], p.Wi - 1);
-    const size_t plane = (size_t)p.Ti * p.Hi * p.Wi, sp = ((size_t)ti * p.Hi + hi) * p.Wi + wi;
+    const Coord c = tap_coord(p, v, j);
+    const size_t plane = (size_t)p.Ti * p.Hi * p.Wi, sp = ((size_t)c.t * p.Hi + c.h) * p.Wi + c.w;
     if (p.in_mode == 0) {
         const T* s = reinterpret_cast<const T*>(p.in) + ((size_t)v.b * plane + sp) * p.Cin;
-        if ((p.Cin & 7) == 0) {
-            if (c0 < p.Cin) {
-                if (sizeof(T) == 2) *reinterpret_cast<u32x4*>(b) = *reinterpret_cast<const u32x4*>(s + c0);
-                else { *reinterpret_cast<u32x4*>(b) = *reinterpret_cast<const u32x4*>(s + c0); *reinterpret_cast<u32x4*>(b + 4) = *reinterpret_cast<const u32x4*>(s + c0 + 4); }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) if (c0 + q < p.Cin) b[q] = s[c0 + q];
-        }
+        load8_cl(s, c0, p.Cin, b);
     } else {
         const float* s = reinterpret_cast<const float*>(p.in) + (size_t)v.b * p.Cin * plane + sp;
 #pragma unroll
@@ -166,9 +146,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const mebt_conv3d_des
         const long m = kb + lv;
         if (m < k1) {
             const Vox v = decode_vox(p, m);
-            const int t = v.t * p.os[0] + p.pi[0], h = v.h * p.os[1] + p.pi[1], w = v.w * p.os[2] + p.pi[2];
-            const size_t ov = (((size_t)v.b * p.To + t) * p.Ho + h) * p.Wo + w;
-            load8_dy<T>(p, ov, co0 + lc, a);
+            load8_dy<T>(p, out_voxel(p, v), co0 + lc, a);
             load8_x<T>(p, v, j, ci0 + lc, b);
         }
         __syncthreads();                                          // the previous k-step's reads are done
@@ -236,25 +214,11 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* part, fl
 // ------------------------------------------------------------------------------------------------
 // GroupNorm + SiLU backward
 // ------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ f32x4 ld4(const T* p);
-template <> __device__ __forceinline__ f32x4 ld4<float>(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-template <> __device__ __forceinline__ f32x4 ld4<f16_t>(const f16_t* p) {
-    const f16x4 v = *reinterpret_cast<const f16x4*>(p);
-    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-}
-template <typename T> __device__ __forceinline__ void st4(T* p, f32x4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-template <> __device__ __forceinline__ void st4<f16_t>(f16_t* p, f32x4 v) {
-    const f16x4 o = {(f16_t)v[0], (f16_t)v[1], (f16_t)v[2], (f16_t)v[3]};
-    *reinterpret_cast<f16x4*>(p) = o;
-}
-
-// xhat and dh = dy * s * (1 + h (1 - s)) of one element; mean / rstd from the forward's {sum, sum of squares} as the forward takes them
+// xhat and dh = dy * s * (1 + h (1 - s)) of one element; mean / rstd from the forward's {sum, sum of squares} by the forward's own gn_mean_rstd
 __device__ __forceinline__ void gn_point(float x, float dy, float sum, float sq, float inv_n, float gamma, float beta, float& xhat, float& dh,
                                          float& rstd) {
-    const float mean = sum * inv_n;
-    const float var = fmaxf(sq * inv_n - mean * mean, 0.f);
-    rstd = rsqrtf(var + 1e-6f);
+    float mean;
+    gn_mean_rstd(sum, sq, inv_n, mean, rstd);
     xhat = (x - mean) * rstd;
     const float h = xhat * gamma + beta;
     const float s = 1.0f / (1.0f + expf(-h));
@@ -283,7 +247,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const T* x, const T
         }
         for (long r = r0 + rl; r < r1; r += rows_par) {
             const size_t e = ((size_t)b * vox + r) * C + c;
-            const f32x4 xv = ld4<T>(x + e), dv = ld4<T>(dy + e);
+            const f32x4 xv = load4<T>(x + e), dv = load4<T>(dy + e);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float xhat, dh, rstd;
@@ -339,7 +303,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* x, const T* 
         const long e = i * 4;
         const int c = (int)(e % C);
         const long b = e / (vox * C);
-        const f32x4 xv = ld4<T>(x + e), dv = ld4<T>(dy + e);
+        const f32x4 xv = load4<T>(x + e), dv = load4<T>(dy + e);
         const f32x4 g4 = *reinterpret_cast<const f32x4*>(gamma + c), b4 = *reinterpret_cast<const f32x4*>(beta + c);
         f32x4 o;
 #pragma unroll
@@ -351,8 +315,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* x, const T* 
             const float m1 = (float)(gs[si] * (double)inv_n), m2 = (float)(gs[si + 1] * (double)inv_n);
             o[j] = rstd * (g4[j] * dh - m1 - xhat * m2);
         }
-        if (add) o += ld4<T>(add + e);
-        st4<T>(dx + e, o);
+        if (add) o += load4<T>(add + e);
+        store4<T>(dx + e, o);
     }
 }
 
@@ -375,15 +339,7 @@ __global__ __launch_bounds__(256) void vq_seed_kernel(const float* z, const floa
     }
 }
 
-unsigned blocks_for(size_t n, unsigned cap) {
-    const size_t b = (n + 255) / 256;
-    return (unsigned)(b < cap ? (b ? b : 1) : cap);
-}
-
 }  // namespace
-
-static hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-static bool dtype_ok(int dtype) { return dtype == MEBT_DTYPE_F32 || dtype == MEBT_DTYPE_F16; }
 
 extern "C" int mebt_op_pad_zero(int32_t dtype, const void* src, void* dst, int32_t B, int32_t T, int32_t H, int32_t W, int32_t fT, int32_t fH,
                                 int32_t fW, int32_t pT, int32_t pH, int32_t pW, int32_t C, int32_t src_mode, mebt_stream_t stream) {
@@ -396,7 +352,7 @@ extern "C" int mebt_op_pad_zero(int32_t dtype, const void* src, void* dst, int32
     if (!total) return MEBT_OK;
     if (!dst || (!src && (size_t)B * T * H * W * C)) { mebt_set_error("pad_zero: null pointer"); return MEBT_EINVAL; }
     const unsigned blocks = blocks_for(total, 65536);
-    if (dtype == MEBT_DTYPE_F16) hipLaunchKernelGGL(pad_zero_kernel<f16_t>, dim3(blocks), dim3(256), 0, S(stream), src, (f16_t*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
+    if (is_f16(dtype)) hipLaunchKernelGGL(pad_zero_kernel<f16_t>, dim3(blocks), dim3(256), 0, S(stream), src, (f16_t*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
     else hipLaunchKernelGGL(pad_zero_kernel<float>, dim3(blocks), dim3(256), 0, S(stream), src, (float*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
@@ -414,7 +370,7 @@ extern "C" int mebt_op_halo_fold(int32_t dtype, const float* dxp, const void* ad
     if (!dxp || !dx) { mebt_set_error("halo_fold: null pointer"); return MEBT_EINVAL; }
     const unsigned blocks = blocks_for(total, 65536);
 #define FOLD(T_, TO_) hipLaunchKernelGGL((halo_fold_kernel<T_, TO_>), dim3(blocks), dim3(256), 0, S(stream), dxp, (const T_*)add, (TO_*)dx, T, H, W, pT, pH, pW, fT, fH, fW, C, (long)total)
-    if (dtype == MEBT_DTYPE_F16) { if (out_mode == 0) FOLD(f16_t, f16_t); else FOLD(f16_t, float); }
+    if (is_f16(dtype)) { if (out_mode == 0) FOLD(f16_t, f16_t); else FOLD(f16_t, float); }
     else FOLD(float, float);
 #undef FOLD
     MEBT_HIP_CHECK(hipGetLastError());
@@ -451,17 +407,11 @@ extern "C" int mebt_op_conv3d_wgrad(int32_t dtype, const mebt_conv3d_desc* d, fl
     if ((long)co_tiles * ci_tiles > 65535) { mebt_set_error("conv3d_wgrad: too many channel tiles"); return MEBT_ESHAPE; }
     const dim3 grid(ns, p.ntaps, co_tiles * ci_tiles);
     float* part = reinterpret_cast<float*>(scratch);
-    if (dtype == MEBT_DTYPE_F16) hipLaunchKernelGGL(conv3d_wgrad_kernel<f16_t>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride);
+    if (is_f16(dtype)) hipLaunchKernelGGL(conv3d_wgrad_kernel<f16_t>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride);
     else hipLaunchKernelGGL(conv3d_wgrad_kernel<float>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride);
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, S(stream), part, dw, db, nw, stride, ns, inv_scale);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
-}
-
-static int gn_rows_per_block(int64_t vox) {
-    int rpb = 64;
-    while ((vox + rpb - 1) / rpb > 512) rpb *= 2;
-    return rpb;
 }
 
 extern "C" int64_t mebt_groupnorm_silu_bwd_scratch_bytes(int32_t B, int64_t vox_per_sample, int32_t C) {
@@ -491,12 +441,14 @@ extern "C" int mebt_op_groupnorm_silu_bwd(int32_t dtype, const void* x, const fl
     const dim3 grid(nslab, B);
     const long total4 = (long)B * vox_per_sample * C / 4;
     const unsigned ablocks = blocks_for((size_t)total4, 8192);
-    if (dtype == MEBT_DTYPE_F16) hipLaunchKernelGGL(gn_bwd_partial_kernel<f16_t>, grid, dim3(256), 0, S(stream), (const f16_t*)x, (const f16_t*)dy, stats, gamma, beta, part, (long)vox_per_sample, C, rpb);
-    else hipLaunchKernelGGL(gn_bwd_partial_kernel<float>, grid, dim3(256), 0, S(stream), (const float*)x, (const float*)dy, stats, gamma, beta, part, (long)vox_per_sample, C, rpb);
-    hipLaunchKernelGGL(gn_bwd_group_kernel, dim3((B * 32 + 63) / 64), dim3(64), 0, S(stream), part, gamma, gs, B, nslab, C);
-    hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, S(stream), part, dgamma, dbeta, B, nslab, C, inv_scale);
-    if (dtype == MEBT_DTYPE_F16) hipLaunchKernelGGL(gn_bwd_apply_kernel<f16_t>, dim3(ablocks), dim3(256), 0, S(stream), (const f16_t*)x, (const f16_t*)dy, (const f16_t*)add, (f16_t*)dx, stats, gs, gamma, beta, (long)vox_per_sample, C, total4);
-    else hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(ablocks), dim3(256), 0, S(stream), (const float*)x, (const float*)dy, (const float*)add, (float*)dx, stats, gs, gamma, beta, (long)vox_per_sample, C, total4);
+    auto run = [&](auto* xt, auto* dyt, auto* addt, auto* dxt) {
+        hipLaunchKernelGGL(gn_bwd_partial_kernel, grid, dim3(256), 0, S(stream), xt, dyt, stats, gamma, beta, part, (long)vox_per_sample, C, rpb);
+        hipLaunchKernelGGL(gn_bwd_group_kernel, dim3((B * 32 + 63) / 64), dim3(64), 0, S(stream), part, gamma, gs, B, nslab, C);
+        hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, S(stream), part, dgamma, dbeta, B, nslab, C, inv_scale);
+        hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ablocks), dim3(256), 0, S(stream), xt, dyt, addt, dxt, stats, gs, gamma, beta, (long)vox_per_sample, C, total4);
+    };
+    if (is_f16(dtype)) run((const f16_t*)x, (const f16_t*)dy, (const f16_t*)add, (f16_t*)dx);
+    else run((const float*)x, (const float*)dy, (const float*)add, (float*)dx);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

@@ -19,8 +19,8 @@ channels-last on the GPU; `compute_dtype` = "f16" (MFMA, BASELINE config 5) or "
 counters are part of the cache key, so an optimizer step is noticed).  No CPU / eager-torch compute path exists.
 """
 import ctypes as C
+import itertools
 import math
-
 import os
 
 import numpy as np
@@ -196,7 +196,7 @@ class Codebook(nn.Module):
         n_total = torch.empty(n_codes, device=z.device, dtype=torch.float32)
         encode_sum = torch.empty(n_codes, d, device=z.device, dtype=torch.float32)
         nbytes = int(lib.mebt_codebook_sums_scratch_bytes(M, n_codes))
-        scratch = torch.empty(max(1, -(-nbytes // 8)), device=z.device, dtype=torch.float64)
+        scratch = _scratch(nbytes, z.device)
         check(lib.mebt_op_codebook_sums(ptr(ids), ptr(z), ptr(n_total), ptr(encode_sum), M, n_codes, d, ptr(scratch), nbytes, cur_stream()))
         return n_total, encode_sum
 
@@ -216,7 +216,7 @@ class Codebook(nn.Module):
         k_rand = None if self.no_random_restart else self.restart_rows(z, restart_src, restart_noise, generator)
         restarted = torch.empty(1, device=z.device, dtype=torch.int32)
         nbytes = int(lib.mebt_codebook_ema_scratch_bytes(self.n_codes))
-        scratch = torch.empty(max(1, -(-nbytes // 8)), device=z.device, dtype=torch.float64)
+        scratch = _scratch(nbytes, z.device)
         check(lib.mebt_op_codebook_ema(ptr(self.N), ptr(self.z_avg), ptr(self.embeddings), ptr(n_total), ptr(encode_sum), ptr(k_rand),
                                        ptr(restarted), self.n_codes, self.embedding_dim, float(self.restart_thres), ptr(scratch), nbytes,
                                        cur_stream()))
@@ -300,7 +300,6 @@ class _Conv:
         leaves it.  A convolution (os = 1) gives one class per parity of q modulo sm (a transposed convolution of dy); a transposed
         one (sm = 1) gives a single strided class over the taps of all its forward classes.  `classes`: dicts os / pi / sm / cq (class
         counts) / taps (into the zero box) / w ([Cin][n][Cout], None for a parity no tap reaches)."""
-        import itertools
         key = tuple(dims)
         if key in self._plans:
             return self._plans[key]
@@ -360,6 +359,27 @@ class _Desc(C.Structure):
                 ("cT", C.c_int32), ("cH", C.c_int32), ("cW", C.c_int32),
                 ("os", C.c_int32 * 3), ("pi", C.c_int32 * 3), ("sm", C.c_int32 * 3), ("ntaps", C.c_int32),
                 ("tap", (C.c_int8 * 4) * 64), ("in_mode", C.c_int32), ("out_mode", C.c_int32)]
+
+    @classmethod
+    def of(cls, x, out, w, B, idims, cin, odims, cout, counts, os_, pi, sm, taps, in_mode, out_mode, bias=None, resid=None):
+        """one class of a convolution: tensors (or None) + the integer geometry of include/mebt_hip.h's mebt_conv3d_desc"""
+        d = cls()
+        d.in_, d.out, d.w, d.bias, d.resid = ptr(x), ptr(out), ptr(w), ptr(bias), ptr(resid)
+        d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, idims[0], idims[1], idims[2], cin
+        d.To, d.Ho, d.Wo, d.Cout = odims[0], odims[1], odims[2], cout
+        d.cT, d.cH, d.cW = counts
+        for k in range(3):
+            d.os[k], d.pi[k], d.sm[k] = os_[k], pi[k], sm[k]
+        d.ntaps = len(taps)
+        for j, t in enumerate(taps):
+            d.tap[j][0], d.tap[j][1], d.tap[j][2] = t
+        d.in_mode, d.out_mode = in_mode, out_mode
+        return d
+
+
+def _scratch(nbytes, device):
+    """at least `nbytes` (and one element) of 8-byte aligned device scratch for an operator that reports its need in bytes"""
+    return torch.empty(max(1, -(-nbytes // 8)), device=device, dtype=torch.float64)
 
 
 class VQGAN(nn.Module):
@@ -480,26 +500,12 @@ class VQGAN(nn.Module):
         dev = x.device
         if self._tape is not None:
             self._tape[name] = (x, dims, in_mode, out_mode)
-        if out_mode == 0:
-            out = torch.empty(B, *od, cv.cout, device=dev, dtype=self._tdt())
-        elif out_mode == 1:
-            out = torch.empty(B, *od, cv.cout, device=dev, dtype=torch.float32)
-        else:
-            out = torch.empty(B, cv.cout, *od, device=dev, dtype=torch.float32)
+        shape = (B, cv.cout, *od) if out_mode == 2 else (B, *od, cv.cout)         # mebt_conv3d_desc.out_mode
+        out = torch.empty(shape, device=dev, dtype=self._tdt() if out_mode == 0 else torch.float32)
         lib = _lib.load()
         for pi, taps, w in cv.classes:
-            d = _Desc()
-            d.in_, d.out, d.w, d.bias, d.resid = ptr(x), ptr(out), ptr(w), ptr(cv.bias), ptr(resid)
-            d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, dims[0], dims[1], dims[2], cv.cin
-            d.To, d.Ho, d.Wo, d.Cout = od[0], od[1], od[2], cv.cout
-            cls = [(o - p + s - 1) // s for o, p, s in zip(od, pi, cv.os)]
-            d.cT, d.cH, d.cW = cls
-            for k in range(3):
-                d.os[k], d.pi[k], d.sm[k] = cv.os[k], pi[k], cv.sm[k]
-            d.ntaps = len(taps)
-            for j, t in enumerate(taps):
-                d.tap[j][0], d.tap[j][1], d.tap[j][2] = t
-            d.in_mode, d.out_mode = in_mode, out_mode
+            d = _Desc.of(x, out, w, B, dims, cv.cin, od, cv.cout, cv.class_counts(od, pi), cv.os, pi, cv.sm, taps, in_mode, out_mode,
+                         bias=cv.bias, resid=resid)
             check(lib.mebt_op_conv3d(self._code(), C.byref(d), 1 if self.use_mfma else 0, cur_stream()))
         return out, od
 
@@ -592,21 +598,6 @@ class VQGAN(nn.Module):
         return self.decode(self.encode(x))
 
     # ---- backward of the reconstruction objective (vqgan.py:98-102,183-184 before discriminator_iter_start) on csrc/vqgan_bwd/vqgan_bwd.hip ----------
-    @staticmethod
-    def _fill_desc(x, out, w, B, idims, cin, odims, cout, cls, os_, pi, sm, taps, in_mode, out_mode):
-        d = _Desc()
-        d.in_, d.out, d.w, d.bias, d.resid = ptr(x), ptr(out), ptr(w), None, None
-        d.B, d.Ti, d.Hi, d.Wi, d.Cin = B, idims[0], idims[1], idims[2], cin
-        d.To, d.Ho, d.Wo, d.Cout = odims[0], odims[1], odims[2], cout
-        d.cT, d.cH, d.cW = cls
-        for k in range(3):
-            d.os[k], d.pi[k], d.sm[k] = os_[k], pi[k], sm[k]
-        d.ntaps = len(taps)
-        for j, t in enumerate(taps):
-            d.tap[j][0], d.tap[j][1], d.tap[j][2] = t
-        d.in_mode, d.out_mode = in_mode, out_mode
-        return d
-
     def _acc(self, param, grad, flags):
         """autograd's accumulate semantics: `.grad` is created where it is None, else added to"""
         flags.append(torch.isfinite(grad).all())
@@ -623,11 +614,11 @@ class VQGAN(nn.Module):
         dws, db = [], None
         for pi, taps, _ in cv.classes:
             cls = cv.class_counts(od, pi)
-            d = self._fill_desc(x, dy, None, B, dims, cv.cin, od, cv.cout, cls, cv.os, pi, cv.sm, taps, in_mode, dy_mode)
+            d = _Desc.of(x, dy, None, B, dims, cv.cin, od, cv.cout, cls, cv.os, pi, cv.sm, taps, in_mode, dy_mode)
             tiles = len(taps) * (-(-cv.cout // 64)) * (-(-cv.cin // 64))
             nsplit = max(1, min(256, -(-1024 // tiles), -(-B * int(np.prod(cls)) // 32)))
             nbytes = int(lib.mebt_conv3d_wgrad_scratch_bytes(C.byref(d), nsplit))
-            scratch = torch.empty(max(1, nbytes // 4), device=x.device, dtype=torch.float32)
+            scratch = _scratch(nbytes, x.device)
             dw = torch.empty(cv.cout, len(taps), cv.cin, device=x.device, dtype=torch.float32)
             dbc = torch.empty(cv.cout, device=x.device, dtype=torch.float32)
             check(lib.mebt_op_conv3d_wgrad(self._code(), C.byref(d), ptr(dw), ptr(dbc), inv_scale, nsplit, ptr(scratch), nbytes, cur_stream()))
@@ -649,7 +640,7 @@ class VQGAN(nn.Module):
         for c in plan["classes"]:
             if c["w"] is None or min(c["cq"]) <= 0:
                 continue
-            d = self._fill_desc(dyz, dxp, c["w"], B, zd, cv.cout, pd, cv.cin, c["cq"], c["os"], c["pi"], c["sm"], c["taps"], 0, 1)
+            d = _Desc.of(dyz, dxp, c["w"], B, zd, cv.cout, pd, cv.cin, c["cq"], c["os"], c["pi"], c["sm"], c["taps"], 0, 1)
             check(lib.mebt_op_conv3d(self._code(), C.byref(d), 1 if self.use_mfma else 0, cur_stream()))
         dx = torch.empty(B, *dims, cv.cin, device=dev, dtype=torch.float32 if out_fp32 else self._tdt())
         check(lib.mebt_op_halo_fold(self._code(), ptr(dxp), ptr(add), ptr(dx), B, *dims, *pd, *fr, cv.cin, 1 if out_fp32 else 0, cur_stream()))
@@ -673,7 +664,7 @@ class VQGAN(nn.Module):
         dx = torch.empty_like(x)
         dg, dbt = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
         nbytes = int(lib.mebt_groupnorm_silu_bwd_scratch_bytes(B, vox, Cc))
-        scratch = torch.empty(max(1, nbytes // 8), device=x.device, dtype=torch.float64)
+        scratch = _scratch(nbytes, x.device)
         check(lib.mebt_op_groupnorm_silu_bwd(self._code(), ptr(x), ptr(stats), ptr(g), ptr(b), ptr(dy), ptr(add), ptr(dx), ptr(dg), ptr(dbt),
                                              inv_scale, B, vox, Cc, ptr(scratch), nbytes, cur_stream()))
         self._acc(gn.weight, dg, flags)

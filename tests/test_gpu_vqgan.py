@@ -35,6 +35,14 @@ def build(name, dtype):
     return m.to(DEV).eval(), cfg, P
 
 
+def _route(host, name, B, dims, in_mode=0, out_mode=0, resid=False):
+    """the kernel `host._conv(name, ...)` runs with these arguments (one name: every class of a layer takes the same route)"""
+    from tests import test_vqgan_route_host as rt
+    from mebt_amd import _lib
+    return rt._one_name(_lib.load(), host._code(), rt._layer_descs(host._prepared["convs"][name], B, dims, in_mode, out_mode, resid),
+                        1 if host.use_mfma else 0)
+
+
 @pytest.mark.parametrize("kind,k,stride,cin,cout", [("conv", 3, (1, 1, 1), 32, 64), ("conv", 4, (2, 2, 2), 32, 64), ("conv", 4, (1, 2, 2), 64, 128),
                                                    ("conv", 1, (1, 1, 1), 64, 64), ("conv", 3, (1, 1, 1), 16, 24),
                                                    ("conv", 3, (1, 1, 1), 64, 64), ("conv", 3, (1, 1, 1), 128, 256),
@@ -42,8 +50,10 @@ def build(name, dtype):
 def test_conv3d_operator(kind, k, stride, cin, cout):
     """mebt_op_conv3d (direct fp32, direct fp16, MFMA fp16: the LDS-DMA kernel where Cin and Cout are multiples of 64 — 256 x 64 and
     128 x 128 tiles, two column tiles at Cout 256, 480 voxels = ragged row tiles — the first MFMA kernel otherwise) vs the oracle's
-    SamePadConv3d / SamePadConvTranspose3d"""
+    SamePadConv3d / SamePadConvTranspose3d; which kernel each leg reaches is asserted (mebt_conv3d_route)"""
+    from tests import test_vqgan_route_host as rt
     from mebt_amd.vqgan import VQGAN, SamePadConv3d, SamePadConvTranspose3d, _Conv
+    mfma_kernel = rt.OPERATOR_F16[rt.OPERATOR_CASES.index((kind, k, stride, cin, cout))]
     g = torch.Generator().manual_seed(k * 100 + cin)
     B, dims = 2, (4, 6, 10)
     x = torch.randn(B, cin, *dims, generator=g)
@@ -64,6 +74,7 @@ def test_conv3d_operator(kind, k, stride, cin, cout):
         cv = _Conv(w.to(DEV), b.to(DEV), (k, k, k), stride, kind == "convt", dtype)
         host._prepared = {"convs": {"t": cv}}
         xin = x.permute(0, 2, 3, 4, 1).contiguous().to(DEV, host._tdt())
+        assert _route(host, "t", B, dims) == _route(host, "t", B, dims, out_mode=1, resid=True) == (mfma_kernel if mfma else "direct")
         out, od = host._conv("t", xin, B, dims)
         assert tuple(out.shape) == tuple(ref_cl.shape) and od == tuple(ref.shape[2:])
         err = (out.float().cpu() - ref_cl).abs().max().item() / ref_cl.abs().max().item()
@@ -77,10 +88,56 @@ def test_conv3d_operator(kind, k, stride, cin, cout):
     # network-boundary layouts: fp32 [B,C,T,H,W] in and out
     host.compute_dtype, host.use_mfma = "f32", False
     host._prepared = {"convs": {"t": _Conv(w.to(DEV), b.to(DEV), (k, k, k), stride, kind == "convt", "f32")}}
+    assert _route(host, "t", B, dims, in_mode=1) == _route(host, "t", B, dims, out_mode=2) == "direct"
     o_in, _ = host._conv("t", x.to(DEV), B, dims, in_mode=1)
     assert (o_in.cpu() - ref_cl).abs().max().item() < 2e-5 * ref_cl.abs().max().item()
     o_out, _ = host._conv("t", x.permute(0, 2, 3, 4, 1).contiguous().to(DEV), B, dims, out_mode=2)
     assert tuple(o_out.shape) == tuple(ref.shape) and (o_out.cpu() - ref).abs().max().item() < 2e-5 * ref.abs().max().item()
+
+
+K3 = (3, 3, 3)
+# 128 -> 3 with 27 taps needs 27 x 4 KB = 108 KB of weight fragments, over conv3d_last_mfma's 96 KB: that shape has always gone to the
+# fp16 voxel kernel.  18 taps (kernel (2, 3, 3)) fit, and reach conv3d_last_mfma<4>.
+THIN_CASES = ([("f16", 3, 32, K3, 1, 0, "first_mfma")]
+              + [("f16", cin, 3, K3, 0, om, name) for cin, name in ((32, "last_mfma_1"), (64, "last_mfma_2"), (128, "voxel_4")) for om in (0, 1, 2)]
+              + [("f16", 128, 3, (2, 3, 3), 0, om, "last_mfma_4") for om in (0, 1, 2)]
+              + [("f32", 32, 3, K3, 0, 0, "voxel_4"), ("f32", 32, 3, K3, 0, 2, "voxel_4"), ("f32", 3, 32, K3, 1, 0, "voxel_32")])
+
+
+@pytest.mark.parametrize("dtype,cin,cout,k,in_mode,out_mode,kernel", THIN_CASES)
+def test_conv3d_thin_layer_kernels(dtype, cin, cout, k, in_mode, out_mode, kernel):
+    """The kernels of the 3-channel boundary layers at operator level, vs the oracle's SamePadConv3d: conv3d_first_mfma (fp32 NCDHW
+    video in), conv3d_last_mfma<1|2|4> in its three output layouts (out_mode 1 with the residual) and conv3d_voxel<4|32> (f32 with MFMA
+    allowed, and f16 where the last layer's weights do not fit).  B = 2, (3, 5, 7) = 210 voxels: ragged for first_mfma's 16-voxel
+    blocks, last_mfma's 64-voxel blocks and the voxel kernel's 256 threads.  In f16 the oracle sees what the kernel multiplies: x
+    (first_mfma rounds the video itself), w and the residual rounded to fp16.  Gates as in test_conv3d_operator: 2e-5 (f32) / 4e-3
+    (f16) of the reference's maximum, x 1.5 with the residual."""
+    from mebt_amd.vqgan import VQGAN, _Conv
+    g = torch.Generator().manual_seed(1000 * cin + 10 * cout + out_mode)
+    B, dims = 2, (3, 5, 7)
+    x = torch.randn(B, cin, *dims, generator=g)
+    w = torch.randn(cout, cin, *k, generator=g) / np.sqrt(cin * np.prod(k))
+    b = torch.randn(cout, generator=g) * 0.1
+    res = torch.randn(B, *dims, cout, generator=g) if out_mode == 1 else None
+    if dtype == "f16":
+        x, w = x.half().float(), w.half().float()
+        res = res.half().float() if res is not None else None
+    ref = vq.same_pad_conv3d(x, w, b, (1, 1, 1))                                   # [B, C, T, H, W]
+    host = VQGAN(argparse.Namespace(n_hiddens=32, downsample=(2, 2, 2), image_channels=3, embedding_dim=32, n_codes=32))
+    host.compute_dtype, host.use_mfma = dtype, True
+    host._prepared = {"convs": {"t": _Conv(w.to(DEV), b.to(DEV), k, (1, 1, 1), False, dtype)}}
+    assert _route(host, "t", B, dims, in_mode, out_mode, res is not None) == kernel
+    xin = x.to(DEV) if in_mode == 1 else x.permute(0, 2, 3, 4, 1).contiguous().to(DEV, host._tdt())
+    out, od = host._conv("t", xin, B, dims, resid=None if res is None else res.to(DEV, host._tdt()), in_mode=in_mode, out_mode=out_mode)
+    assert od == dims and out.dtype == (host._tdt() if out_mode == 0 else torch.float32)
+    want = ref if out_mode == 2 else ref.permute(0, 2, 3, 4, 1).contiguous()
+    if res is not None:
+        want = want + res
+    assert tuple(out.shape) == tuple(want.shape)
+    err = (out.float().cpu() - want).abs().max().item() / ref.abs().max().item()
+    tol = (2e-5 if dtype == "f32" else 4e-3) * (1.5 if res is not None else 1.0)
+    print(f"[thin conv {kernel} out_mode {out_mode}] rel err {err:.2e} (gate {tol:.1e})")
+    assert err < tol, (kernel, out_mode, err)
 
 
 @pytest.mark.parametrize("C", [32, 64, 256])
