@@ -280,6 +280,81 @@ int mebt_op_next_mask(const int64_t* ci, const int64_t* ti, const float* score, 
 /* fp32 -> bf16 cast of a flat buffer (n multiple of 4). */
 int mebt_op_cast_bf16(const float* src, void* dst, int64_t n, mebt_stream_t stream);
 
+/* ---- the row kernels in every form the engine launches (what tests/test_gpu_row_ops.py calls) ------
+ * Thin marshalling onto the launchers of the train step.  Every refusal (null required pointer, bad dtype, a width that is no
+ * multiple of 4, too many jobs) is decided on the host before anything is launched; empty shapes return 0 and launch nothing. */
+#define MEBT_LN_MAX_JOBS 3
+/* One LayerNorm of a multi-job launch.  Row r of `x` belongs to row map(r) = (r / seg) * seg_stride + seg_off + r % seg of the
+ * mapped tensors (seg = 0: identity).  Forward: y, mean, rstd are written at the mapped row (mean = rstd = NULL: inference form).
+ * Backward: dy, mean, rstd are read at the mapped row, x / dy2 / dx_add / dx / dx2 at the plain row, and
+ *   dx = LN'(dy + dy2) + (dx_add + old dx)      (dy2, dx_add optional; old dx only with dx_accumulate)
+ * dx_f32 = 1: dx / dx2 are fp32 although the job is bf16.  dx2 (optional) = stored dx * the keep-scale of dropout site
+ * (drop_seed, drop_site, drop_p) at element row * d + e, as mebt_debug_dropout_mask returns it; drop_p = 0: no mask.
+ * dgamma / dbeta (fp32) are added to.  Jobs with rows <= 0 are skipped and do not count towards MEBT_LN_MAX_JOBS. */
+typedef struct mebt_ln_job {
+    const void* x;
+    void* y;
+    const void* dy;
+    const void* dy2;
+    const void* dx_add;
+    const float* gamma;
+    const float* beta;
+    float* mean;
+    float* rstd;
+    void* dx;
+    void* dx2;
+    float* dgamma;
+    float* dbeta;
+    int32_t rows, d, seg, seg_stride, seg_off;
+    int32_t dx_f32, dx_accumulate;
+    uint32_t drop_site;
+    uint64_t drop_seed;
+    float drop_p;
+    int32_t reserved;
+} mebt_ln_job;
+/* out[n] += sum_m X[m, n]: X [M, N] of `dtype` at row pitch ldx (elements, a multiple of 4), N a multiple of 4, out fp32 */
+typedef struct mebt_colsum_item {
+    const void* X;
+    float* out;
+    int32_t M, N, ldx;
+    int32_t reserved;
+} mebt_colsum_item;
+int mebt_op_layernorm_fwd_jobs(int32_t dtype, const mebt_ln_job* jobs, int32_t n, mebt_stream_t stream);
+/* n_colsums > 0: these column sums (at most 12) are computed by extra workgroups of the same launch */
+int mebt_op_layernorm_bwd_jobs(int32_t dtype, const mebt_ln_job* jobs, int32_t n, const mebt_colsum_item* colsums, int32_t n_colsums,
+                               mebt_stream_t stream);
+int mebt_op_colsum(int32_t dtype, const void* X, int32_t M, int32_t N, int32_t ldx, float* out, mebt_stream_t stream);
+int mebt_op_colsum_grouped(int32_t dtype, const mebt_colsum_item* items, int32_t n, mebt_stream_t stream);
+/* The masked-token loss of rows = B * NT logit rows [rows, V] fp32 (V a multiple of 4); the target of row (b, j) is
+ * x_ids[b, ti[b, j]].  Per row: row_lse, row_loss (label-smoothed), row_rank (classes ranked above the target; among equal logits
+ * the lower index ranks higher); out4 (double): loss sum, top-1 count, top-5 count, rows.  dlogits (optional, fp32 or bf16 by
+ * dl_bf16) = d(loss sum * grad_scale) / dlogits from the same pass: V = 16384 only, left untouched at every other V. */
+int mebt_op_cross_entropy(const float* logits, const int64_t* x_ids, const int64_t* ti, int32_t B, int32_t N, int32_t NT, int32_t V,
+                          float label_smoothing, float* row_lse, float* row_loss, int32_t* row_rank, double* out4, void* dlogits,
+                          int32_t dl_bf16, float grad_scale, mebt_stream_t stream);
+/* dlogits [rows, V] of `dtype` = (softmax - smoothed one-hot) * scale * (*upstream, a device scalar, or 1 when NULL) */
+int mebt_op_cross_entropy_bwd(int32_t dtype, const float* logits, const int64_t* x_ids, const int64_t* ti, const float* row_lse,
+                              const float* upstream, float scale, float label_smoothing, void* dlogits, int32_t B, int32_t N,
+                              int32_t NT, int32_t V, mebt_stream_t stream);
+/* AdamW (torch.optim.AdamW semantics) over a flat buffer of n elements (a multiple of 4), step >= 1; p_bf16 (optional): bf16 mirror of
+ * the updated p.  g is fp32, or (g_bf16) the fp32 sum of g_pieces bf16 copies, copy j at g + j * g_stride elements. */
+int mebt_op_adamw(float* p, const void* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, int32_t step, float grad_scale, int32_t g_bf16, int32_t g_pieces, int64_t g_stride,
+                  mebt_stream_t stream);
+/* Backward of mebt_op_embed_fwd: g_ctx [B, NC, d] fp32, g_tgt [B, NT, d] and g_sos [B, NS, d] of `dtype` are added into the fp32
+ * gradients of tok_emb / pos_emb (by token and position), mask_emb (all target rows) and sos_emb (over the batch). */
+int mebt_op_embed_bwd(int32_t dtype, const int64_t* x_ids, const int64_t* ci, const int64_t* ti, const float* g_ctx, const void* g_tgt,
+                      const void* g_sos, float* g_tok_emb, float* g_pos_emb, float* g_mask_emb, float* g_sos_emb, int32_t B, int32_t N,
+                      int32_t NC, int32_t NT, int32_t NS, int32_t d, mebt_stream_t stream);
+/* dst[map_d(r)] = src[map_s(r)] for r < rows, rows of d elements (a multiple of 4), fp32 or bf16 on either side (bf16 stores round
+ * to nearest even); map(r) = (r / seg) * stride + off + r % seg, seg = 0: identity */
+int mebt_op_copy_rows(const void* src, void* dst, int64_t rows, int32_t d, int32_t src_f32, int32_t dst_f32, int32_t s_seg,
+                      int32_t s_stride, int32_t s_off, int32_t d_seg, int32_t d_stride, int32_t d_off, mebt_stream_t stream);
+/* rows of row_bytes bytes (a multiple of 16) moved by idx [B, n]: gather dst[b * n + j] = src[b * npos + idx[b, j]], scatter the
+ * inverse; positions outside [0, npos) are skipped */
+int mebt_op_index_rows(const void* src, void* dst, const int64_t* idx, int32_t B, int32_t n, int32_t npos, int32_t row_bytes,
+                       int32_t scatter, mebt_stream_t stream);
+
 /* 0: never time GEMM candidates (measured heuristic or cached choices only: no host synchronisation anywhere);
  * 1: tune unseen signatures at their first launch (default; environment MEBT_GEMM_AUTOTUNE). */
 void mebt_gemm_autotune(int32_t mode);

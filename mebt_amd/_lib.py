@@ -27,6 +27,23 @@ class ModelDesc(C.Structure):
                 ("embd_pdrop", c_f32), ("resid_pdrop", c_f32), ("attn_pdrop", c_f32)]
 
 
+class LnJob(C.Structure):
+    """mebt_ln_job of include/mebt_hip.h: one LayerNorm of a multi-job launch"""
+    _fields_ = [("x", c_vp), ("y", c_vp), ("dy", c_vp), ("dy2", c_vp), ("dx_add", c_vp), ("gamma", c_vp), ("beta", c_vp),
+                ("mean", c_vp), ("rstd", c_vp), ("dx", c_vp), ("dx2", c_vp), ("dgamma", c_vp), ("dbeta", c_vp),
+                ("rows", c_i32), ("d", c_i32), ("seg", c_i32), ("seg_stride", c_i32), ("seg_off", c_i32),
+                ("dx_f32", c_i32), ("dx_accumulate", c_i32), ("drop_site", C.c_uint32), ("drop_seed", C.c_uint64),
+                ("drop_p", c_f32), ("reserved", c_i32)]
+
+
+class ColsumItem(C.Structure):
+    """mebt_colsum_item of include/mebt_hip.h"""
+    _fields_ = [("X", c_vp), ("out", c_vp), ("M", c_i32), ("N", c_i32), ("ldx", c_i32), ("reserved", c_i32)]
+
+
+MEBT_LN_MAX_JOBS = 3
+
+
 # name -> (restype, argtypes); every symbol declared in include/mebt_hip.h
 PROTOTYPES = {
     "mebt_last_error": (C.c_char_p, []),
@@ -75,6 +92,16 @@ PROTOTYPES = {
     "mebt_op_scatter_ids": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_next_mask": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "mebt_op_cast_bf16": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
+    "mebt_op_layernorm_fwd_jobs": (c_i32, [c_i32, C.POINTER(LnJob), c_i32, c_vp]),
+    "mebt_op_layernorm_bwd_jobs": (c_i32, [c_i32, C.POINTER(LnJob), c_i32, C.POINTER(ColsumItem), c_i32, c_vp]),
+    "mebt_op_colsum": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mebt_op_colsum_grouped": (c_i32, [c_i32, C.POINTER(ColsumItem), c_i32, c_vp]),
+    "mebt_op_cross_entropy": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp]),
+    "mebt_op_cross_entropy_bwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mebt_op_adamw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32, c_f32, c_i32, c_i32, c_i64, c_vp]),
+    "mebt_op_embed_bwd": (c_i32, [c_i32] + [c_vp] * 10 + [c_i32] * 6 + [c_vp]),
+    "mebt_op_copy_rows": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mebt_op_index_rows": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_conv3d": (c_i32, [c_i32, c_vp, c_i32, c_vp]),
     "mebt_conv3d_route": (C.c_char_p, [c_i32, c_vp, c_i32]),
     "mebt_op_groupnorm_silu": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),

@@ -266,3 +266,172 @@ extern "C" int mebt_op_cast_bf16(const float* src, void* dst, int64_t n, mebt_st
     if (!src || !dst) { mebt_set_error("cast: null pointer"); return MEBT_EINVAL; }
     return launch_cast_f32_to_bf16(src, dst, (size_t)n, S(stream));
 }
+
+// ---- the row kernels in every form the engine launches (include/mebt_hip.h; tests/test_gpu_row_ops.py) -------------------------
+// Every refusal below is decided before the first HIP call, and an empty shape returns before any: both hold without a device.
+static_assert(MEBT_LN_MAX_JOBS == MEBT_LN_MAXJ, "the public job limit is the launchers'");
+static int ln_job_shape(const mebt_ln_job& j) {
+    if (j.d <= 0 || j.d % 4 || j.d > 2048) { mebt_set_error("layernorm: d must be a multiple of 4 and <= 2048"); return MEBT_ESHAPE; }
+    if (j.seg < 0 || (j.seg > 0 && (j.seg_stride < j.seg || j.seg_off < 0))) { mebt_set_error("layernorm: bad row map (seg >= 0, seg_stride >= seg, seg_off >= 0)"); return MEBT_ESHAPE; }
+    return MEBT_OK;
+}
+// the live jobs (rows > 0) of a launch: at most MEBT_LN_MAXJ
+static int ln_live_jobs(const mebt_ln_job* jobs, int32_t n, const mebt_ln_job** live, int& k) {
+    k = 0;
+    if (n < 0 || (n > 0 && !jobs)) { mebt_set_error("layernorm: bad job list"); return MEBT_EINVAL; }
+    for (int i = 0; i < n; ++i) {
+        if (jobs[i].rows <= 0) continue;
+        if (k == MEBT_LN_MAXJ) { mebt_set_error("layernorm: too many jobs in one launch"); return MEBT_EINVAL; }
+        live[k++] = &jobs[i];
+    }
+    return MEBT_OK;
+}
+static int colsum_items(const mebt_colsum_item* items, int32_t n, GroupedColsum& c) {
+    if (n < 0 || n > MEBT_MAX_GROUP || (n > 0 && !items)) { mebt_set_error("colsum: bad item list (at most 12 items)"); return MEBT_EINVAL; }
+    c.n = 0;
+    for (int i = 0; i < n; ++i) {
+        const mebt_colsum_item& it = items[i];
+        if (it.M <= 0 || it.N <= 0) continue;
+        if (!it.X || !it.out) { mebt_set_error("colsum: null pointer"); return MEBT_EINVAL; }
+        if (it.N % 4 || it.ldx % 4 || it.ldx < it.N) { mebt_set_error("colsum: N and ldx must be multiples of 4, ldx >= N"); return MEBT_ESHAPE; }
+        c.g[c.n++] = GroupedColsum::Item{it.X, it.out, it.M, it.N, it.ldx, 0, 0};
+    }
+    return MEBT_OK;
+}
+
+extern "C" int mebt_op_layernorm_fwd_jobs(int32_t dtype, const mebt_ln_job* jobs, int32_t n, mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    const mebt_ln_job* live[MEBT_LN_MAXJ];
+    int k = 0;
+    if (int rc = ln_live_jobs(jobs, n, live, k)) return rc;
+    LnFwdParams p[MEBT_LN_MAXJ];
+    for (int i = 0; i < k; ++i) {
+        const mebt_ln_job& j = *live[i];
+        if (!j.x || !j.y || !j.gamma || !j.beta || ((j.mean != nullptr) != (j.rstd != nullptr))) { mebt_set_error("layernorm: null pointer (mean and rstd go together)"); return MEBT_EINVAL; }
+        if (int rc = ln_job_shape(j)) return rc;
+        p[i].x = j.x; p[i].y = j.y; p[i].gamma = j.gamma; p[i].beta = j.beta; p[i].mean = j.mean; p[i].rstd = j.rstd;
+        p[i].rows = j.rows; p[i].d = j.d; p[i].seg = j.seg; p[i].seg_stride = j.seg_stride; p[i].seg_off = j.seg_off;
+    }
+    return k ? launch_ln_fwd_multi(p, k, dtype, S(stream)) : MEBT_OK;
+}
+
+extern "C" int mebt_op_layernorm_bwd_jobs(int32_t dtype, const mebt_ln_job* jobs, int32_t n, const mebt_colsum_item* colsums, int32_t n_colsums,
+                                          mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    const mebt_ln_job* live[MEBT_LN_MAXJ];
+    int k = 0;
+    if (int rc = ln_live_jobs(jobs, n, live, k)) return rc;
+    LnBwdParams p[MEBT_LN_MAXJ];
+    for (int i = 0; i < k; ++i) {
+        const mebt_ln_job& j = *live[i];
+        if (!j.x || !j.dy || !j.gamma || !j.mean || !j.rstd || !j.dx || !j.dgamma || !j.dbeta) { mebt_set_error("layernorm_bwd: null pointer"); return MEBT_EINVAL; }
+        if (int rc = ln_job_shape(j)) return rc;
+        if (!(j.drop_p >= 0.f && j.drop_p < 1.f)) { mebt_set_error("layernorm_bwd: drop_p must be in [0, 1)"); return MEBT_EINVAL; }
+        LnBwdParams& q = p[i];
+        q.x = j.x; q.dy = j.dy; q.dy2 = j.dy2; q.dx_add = j.dx_add; q.gamma = j.gamma; q.mean = j.mean; q.rstd = j.rstd;
+        q.dx = j.dx; q.dx_f32 = (dtype == MEBT_F32 || j.dx_f32) ? 1 : 0; q.dx_accumulate = j.dx_accumulate ? 1 : 0;
+        q.dgamma = j.dgamma; q.dbeta = j.dbeta; q.rows = j.rows; q.d = j.d; q.seg = j.seg; q.seg_stride = j.seg_stride; q.seg_off = j.seg_off;
+        q.dx2 = j.dx2; q.drop2 = make_drop(j.drop_seed, j.drop_site, j.drop_p);
+    }
+    GroupedColsum cs;
+    if (int rc = colsum_items(colsums, n_colsums, cs)) return rc;
+    if (!k) return cs.n ? launch_colsum_grouped(cs, dtype, S(stream)) : MEBT_OK;
+    return launch_ln_bwd_multi(p, k, dtype, S(stream), cs.n ? &cs : nullptr);
+}
+
+extern "C" int mebt_op_colsum(int32_t dtype, const void* X, int32_t M, int32_t N, int32_t ldx, float* out, mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    const mebt_colsum_item it = {X, out, M, N, ldx, 0};
+    GroupedColsum one;
+    if (int rc = colsum_items(&it, 1, one)) return rc;
+    return one.n ? launch_colsum(X, M, N, ldx, out, dtype, S(stream)) : MEBT_OK;
+}
+
+extern "C" int mebt_op_colsum_grouped(int32_t dtype, const mebt_colsum_item* items, int32_t n, mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    GroupedColsum cs;
+    if (int rc = colsum_items(items, n, cs)) return rc;
+    return cs.n ? launch_colsum_grouped(cs, dtype, S(stream)) : MEBT_OK;
+}
+
+static int ce_shape(int32_t B, int32_t N, int32_t NT, int32_t V) {
+    if (B < 0 || N < 0 || NT < 0 || NT > N) { mebt_set_error("cross-entropy: need B >= 0 and 0 <= NT <= N"); return MEBT_ESHAPE; }
+    if (V <= 0 || V % 4) { mebt_set_error("cross-entropy: V must be a positive multiple of 4"); return MEBT_ESHAPE; }
+    return MEBT_OK;
+}
+
+// B * NT = 0: nothing is launched (out4 is left as it is)
+extern "C" int mebt_op_cross_entropy(const float* logits, const int64_t* x_ids, const int64_t* ti, int32_t B, int32_t N, int32_t NT, int32_t V,
+                                     float label_smoothing, float* row_lse, float* row_loss, int32_t* row_rank, double* out4, void* dlogits,
+                                     int32_t dl_bf16, float grad_scale, mebt_stream_t stream) {
+    if (int rc = ce_shape(B, N, NT, V)) return rc;
+    if ((long)B * NT == 0) return MEBT_OK;
+    if (!logits || !x_ids || !ti || !row_lse || !row_loss || !row_rank || !out4) { mebt_set_error("cross-entropy: null pointer"); return MEBT_EINVAL; }
+    CeParams p;
+    p.logits = logits; p.x_ids = x_ids; p.ti = ti; p.rows = B * NT; p.V = V; p.B = B; p.N = N; p.NT = NT; p.label_smoothing = label_smoothing;
+    p.row_lse = row_lse; p.row_loss = row_loss; p.row_rank = row_rank; p.out = out4;
+    p.dlogits = dlogits; p.grad_scale = grad_scale; p.dl_bf16 = dl_bf16 ? 1 : 0;
+    return launch_ce_fwd(p, S(stream));
+}
+
+extern "C" int mebt_op_cross_entropy_bwd(int32_t dtype, const float* logits, const int64_t* x_ids, const int64_t* ti, const float* row_lse,
+                                         const float* upstream, float scale, float label_smoothing, void* dlogits, int32_t B, int32_t N,
+                                         int32_t NT, int32_t V, mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    if (int rc = ce_shape(B, N, NT, V)) return rc;
+    if ((long)B * NT == 0) return MEBT_OK;
+    if (!logits || !x_ids || !ti || !row_lse || !dlogits) { mebt_set_error("cross-entropy_bwd: null pointer"); return MEBT_EINVAL; }
+    CeBwdParams p;
+    p.logits = logits; p.x_ids = x_ids; p.ti = ti; p.row_lse = row_lse; p.dlogits = dlogits; p.upstream = upstream; p.scale = scale;
+    p.label_smoothing = label_smoothing; p.rows = B * NT; p.V = V; p.B = B; p.N = N; p.NT = NT;
+    return launch_ce_bwd(p, dtype, S(stream));
+}
+
+extern "C" int mebt_op_adamw(float* p, const void* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int32_t step, float grad_scale, int32_t g_bf16, int32_t g_pieces, int64_t g_stride,
+                             mebt_stream_t stream) {
+    if (n < 0 || step < 1 || g_pieces < 1) { mebt_set_error("adamw: need n >= 0, step >= 1 and g_pieces >= 1"); return MEBT_EINVAL; }
+    if (n % 4) { mebt_set_error("adamw: flat buffer length must be a multiple of 4"); return MEBT_ESHAPE; }
+    if (g_pieces > 1 && (!g_bf16 || g_stride < n || g_stride % 4)) { mebt_set_error("adamw: gradient pieces are bf16, g_stride >= n and a multiple of 4"); return MEBT_ESHAPE; }
+    if (n == 0) return MEBT_OK;
+    if (!p || !g || !m || !v) { mebt_set_error("adamw: null pointer"); return MEBT_EINVAL; }
+    AdamWParams a;
+    a.p = p; a.g = reinterpret_cast<const float*>(g); a.m = m; a.v = v; a.p_bf16 = p_bf16; a.n = (size_t)n;
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+    a.bc1 = (float)(1.0 - pow((double)beta1, step)); a.bc2 = (float)(1.0 - pow((double)beta2, step)); a.grad_scale = grad_scale;
+    a.g_bf16 = g_bf16 ? 1 : 0; a.g_pieces = g_pieces; a.g_stride = (size_t)g_stride;
+    return launch_adamw(a, S(stream));
+}
+
+extern "C" int mebt_op_embed_bwd(int32_t dtype, const int64_t* x_ids, const int64_t* ci, const int64_t* ti, const float* g_ctx, const void* g_tgt,
+                                 const void* g_sos, float* g_tok_emb, float* g_pos_emb, float* g_mask_emb, float* g_sos_emb, int32_t B, int32_t N,
+                                 int32_t NC, int32_t NT, int32_t NS, int32_t d, mebt_stream_t stream) {
+    if (int rc = check_dtype(dtype)) return rc;
+    if (B < 0 || N < 0 || NC < 0 || NT < 0 || NS < 0 || NC + NT > N) { mebt_set_error("embed_bwd: bad extents (NC + NT <= N)"); return MEBT_ESHAPE; }
+    if (d <= 0 || d % 4) { mebt_set_error("embed_bwd: d must be a positive multiple of 4"); return MEBT_ESHAPE; }
+    if (B == 0 || NC + NT + NS == 0) return MEBT_OK;
+    if ((NC > 0 && (!x_ids || !ci || !g_ctx || !g_tok_emb)) || (NT > 0 && (!ti || !g_tgt || !g_mask_emb)) || (NC + NT > 0 && !g_pos_emb) ||
+        (NS > 0 && (!g_sos || !g_sos_emb))) { mebt_set_error("embed_bwd: null pointer"); return MEBT_EINVAL; }
+    EmbedBwdParams p;
+    p.x_ids = x_ids; p.ci = ci; p.ti = ti; p.g_ctx = g_ctx; p.g_tgt = g_tgt; p.g_sos = g_sos;
+    p.g_tok_emb = g_tok_emb; p.g_pos_emb = g_pos_emb; p.g_mask_emb = g_mask_emb; p.g_sos_emb = g_sos_emb;
+    p.B = B; p.N = N; p.NC = NC; p.NT = NT; p.NS = NS; p.d = d;
+    return launch_embed_bwd(p, dtype, S(stream));
+}
+
+extern "C" int mebt_op_copy_rows(const void* src, void* dst, int64_t rows, int32_t d, int32_t src_f32, int32_t dst_f32, int32_t s_seg,
+                                 int32_t s_stride, int32_t s_off, int32_t d_seg, int32_t d_stride, int32_t d_off, mebt_stream_t stream) {
+    if (d > 0 && d % 4) { mebt_set_error("copy_rows: d must be a multiple of 4"); return MEBT_ESHAPE; }
+    if (s_seg < 0 || d_seg < 0) { mebt_set_error("copy_rows: bad row map"); return MEBT_ESHAPE; }
+    if (rows <= 0 || d <= 0) return MEBT_OK;
+    if (!src || !dst) { mebt_set_error("copy_rows: null pointer"); return MEBT_EINVAL; }
+    return launch_copy_rows(src, dst, (long)rows, d, src_f32 ? 1 : 0, dst_f32 ? 1 : 0, s_seg, s_stride, s_off, d_seg, d_stride, d_off, S(stream));
+}
+
+extern "C" int mebt_op_index_rows(const void* src, void* dst, const int64_t* idx, int32_t B, int32_t n, int32_t npos, int32_t row_bytes,
+                                  int32_t scatter, mebt_stream_t stream) {
+    if (row_bytes <= 0 || row_bytes % 16) { mebt_set_error("index_rows: rows must be a multiple of 16 bytes"); return MEBT_ESHAPE; }
+    if (B <= 0 || n <= 0) return MEBT_OK;
+    if (!src || !dst || !idx) { mebt_set_error("index_rows: null pointer"); return MEBT_EINVAL; }
+    return launch_index_rows(src, dst, idx, B, n, npos, row_bytes, scatter ? 1 : 0, S(stream));
+}
