@@ -236,3 +236,19 @@ def ptr(t):
 def cur_stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def dtype_code(name):
+    """compute dtype "f16" / "f32" -> the C ABI's dtype code"""
+    return F16 if name == "f16" else F32
+
+
+def torch_dtype(name):
+    import torch
+    return torch.float16 if name == "f16" else torch.float32
+
+
+def scratch(nbytes, device):
+    """at least `nbytes` (and one element) of 8-byte aligned device scratch for an operator that reports its need in bytes"""
+    import torch
+    return torch.empty(max(1, -(-nbytes // 8)), device=device, dtype=torch.float64)

@@ -11,10 +11,8 @@
 // partials in the same fixed order.  Every product and sum of the update is a separately rounded fp32 operation (__fmul_rn /
 // __fadd_rn / __fdiv_rn): nothing contracts into an FMA.  Every offset into an operand is 64-bit.
 #include <cmath>
-#include <cstdio>
 
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+#include "../host_util.h"
 
 // hipcc contracts a * b + c into an FMA by default, and HIP's __fmul_rn / __fadd_rn are inline functions around the plain operators that
 // carry the translation unit's contraction setting: the Makefile compiles this file with -ffp-contract=off, which is what keeps every
@@ -251,16 +249,7 @@ __global__ __launch_bounds__(CT_THREADS) void restart_rows_kernel(const float* _
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-int fail(int code, const char* who, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    mebt_set_error(msg);
-    return code;
-}
-
+// this file's slabs start on 16 bytes and carry no workgroup bound: an overload of host_util.h's check, not a copy
 int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need) {
     if (!scratch) return fail(MEBT_EINVAL, who, "null pointer");
     if (reinterpret_cast<uintptr_t>(scratch) & 15) return fail(MEBT_EINVAL, who, "scratch must be 16-byte aligned");

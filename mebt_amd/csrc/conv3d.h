@@ -2,8 +2,7 @@
 // coordinates, the input voxel a tap reads (replicate padding IS the clamp in tap_coord: the one definition of SamePadConv3d's border), an output
 // voxel's place in the three output layouts, GroupNorm's {sum, sum of squares} -> mean and rstd, and the launchers' small host helpers.
 #pragma once
-#include "common.h"
-#include "../../include/mebt_hip.h"
+#include "host_util.h"
 
 namespace {
 
@@ -61,8 +60,7 @@ __device__ __forceinline__ void gn_mean_rstd(float sum, float sq, float inv_n, f
     rstd = rsqrtf(var + 1e-6f);
 }
 
-// ---- host ---------------------------------------------------------------------------------------------------------------
-inline hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+// ---- host (S and the other entry-point helpers: host_util.h) ---------------------------------------------------------------
 inline bool dtype_ok(int dtype) { return dtype == MEBT_DTYPE_F32 || dtype == MEBT_DTYPE_F16; }
 inline bool is_f16(int dtype) { return dtype == MEBT_DTYPE_F16; }
 // 256-thread blocks for n items, at least 1 and at most `cap` (grid-stride kernels)

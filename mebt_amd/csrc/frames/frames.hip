@@ -15,10 +15,7 @@
 // FVD): the resampled byte goes through a 256-entry uint8 table instead (the reference's `((video + 0.5) * 255).byte()`, built on the
 // host: mebt_amd/frames.py:byte_table) and is stored as the I3D path's clip [B, T, R, R, 3].  There a frame is R rows of R * 3 bytes
 // and a channel is just a column, so the vertical pass writes the tile's contiguous run of output bytes a dword per lane (byte_run.h).
-#include <string>
-
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+#include "../host_util.h"
 #include "byte_run.h"
 
 namespace {
@@ -249,12 +246,7 @@ __global__ __launch_bounds__(FR_THREADS) void video_to_clip_kernel(const float* 
     write_run(run, nrun, c0, c1, ch.j0 + 4 * tid, 4 * FR_THREADS, [&](int j) { return buf[s0 + j]; });
 }
 
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-
-int fail(const char* who, const char* what) {
-    mebt_set_error((std::string(who) + ": " + what).c_str());
-    return MEBT_EINVAL;
-}
+int fail(const char* who, const char* what) { return fail(MEBT_EINVAL, who, what); }     // every refusal of this file is MEBT_EINVAL
 
 // grid of the two chunked kernels over `nframes` runs of nrun bytes: one block per (run, chunk); `out` as in run_chunks
 int chunk_grid(const char* who, long nrun, const void* out, long nframes, int* nchunk, unsigned* blocks) {

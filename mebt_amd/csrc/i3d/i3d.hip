@@ -12,22 +12,15 @@
 // the chunk width) or for every element (Conv3d_1a, Cin = 3, K = 1029: no padding of Cin to 4); the k-loop then gathers without
 // integer division.  The row of an output voxel is fixed for the whole k-loop and its accumulation order never depends on M or
 // on the tile it sits in, so a clip's result does not depend on the batch it is part of.
-#include "../common.h"
+#include "../host_util.h"
 #include "../kernels.h"
-#include "../../../include/mebt_hip.h"
+#include "../mfma_tile.h"
 #include <math.h>
 
 namespace {
 
-constexpr int I3D_BK = 32;
-constexpr int I3D_BN = 64;
+constexpr int I3D_BK = TILE_BK, I3D_BN = TILE_BN;
 constexpr int I3D_MAX_TAB = 2048;      // LDS entries of the K table (8 KiB)
-
-template <typename T> struct ConvCfg;
-// fp16: 128 x 64 tiles, each wave 32 rows (two 16-row blocks) x 64 columns, v_mfma_f32_16x16x32_f16
-template <> struct ConvCfg<f16_t> { static constexpr int VEC = 8, WM = 2, BM = 128, LD = 40; };
-// fp32: 64 x 64 tiles, each wave 16 rows x 64 columns, v_mfma_f32_16x16x4_f32 (an exact fp32 FMA chain)
-template <> struct ConvCfg<float> { static constexpr int VEC = 4, WM = 1, BM = 64, LD = 36; };
 
 __device__ __forceinline__ uint32_t tab_entry(const mebt_i3d_conv_desc& p, int k, int K) {
     if (k >= K) return 0u;
@@ -51,7 +44,7 @@ __device__ __forceinline__ bool tap_offset(const mebt_i3d_conv_desc& p, const Ro
 
 template <typename T>
 __global__ __launch_bounds__(256) void i3d_conv_kernel(const mebt_i3d_conv_desc p, int vec_mode, int Kpad) {
-    using Cfg = ConvCfg<T>;
+    using Cfg = TileCfg<T>;
     constexpr int VEC = Cfg::VEC, BM = Cfg::BM, LD = Cfg::LD, WM = Cfg::WM;
     constexpr int ACH = BM * I3D_BK / VEC / 256;       // A chunks per thread (2)
     constexpr int BCH = I3D_BN * I3D_BK / VEC / 256;   // B chunks per thread (1 fp16, 2 fp32)
@@ -93,12 +86,8 @@ __global__ __launch_bounds__(256) void i3d_conv_kernel(const mebt_i3d_conv_desc 
     for (int i = 0; i < BCH; ++i) { const int id = tid + 256 * i; brow[i] = id / CPR; bch[i] = id % CPR; }
     __syncthreads();                                   // the K table
 
-    constexpr int NACC = Cfg::WM;
-    f32x4 acc[NACC][4];
-#pragma unroll
-    for (int i = 0; i < NACC; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[WM][4];
+    tile_zero(acc);
 
     u32x4 ra[ACH], rb[BCH];
     auto gload = [&](int kk) {
@@ -139,36 +128,18 @@ __global__ __launch_bounds__(256) void i3d_conv_kernel(const mebt_i3d_conv_desc 
     for (int kk = 0; kk < nk; ++kk) {
         const int s = kk & 1;
         if (kk + 1 < nk) gload(kk + 1);
-        if constexpr (sizeof(T) == 2) {
-            f16x8 af[NACC], bf[4];
+        int ar[WM], br[4];
 #pragma unroll
-            for (int i = 0; i < NACC; ++i) af[i] = *reinterpret_cast<const f16x8*>(&sA[s][(16 * WM * wave + 16 * i + fr) * LD + fq * 8]);
+        for (int i = 0; i < WM; ++i) ar[i] = (16 * WM * wave + 16 * i + fr) * LD;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(&sB[s][(16 * j + fr) * LD + fq * 8]);
-#pragma unroll
-            for (int i = 0; i < NACC; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int q = 0; q < I3D_BK / 4; ++q) {
-                float af[NACC], bf[4];
-#pragma unroll
-                for (int i = 0; i < NACC; ++i) af[i] = sA[s][(16 * WM * wave + 16 * i + fr) * LD + 4 * q + fq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bf[j] = sB[s][(16 * j + fr) * LD + 4 * q + fq];
-#pragma unroll
-                for (int i = 0; i < NACC; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j], af[i], acc[i][j], 0, 0, 0);
-            }
-        }
+        for (int j = 0; j < 4; ++j) br[j] = (16 * j + fr) * LD;
+        tile_mma<T, WM>(acc, sA[s], ar, sB[s], br, fq);
         if (kk + 1 < nk) lstore(s ^ 1);
         __syncthreads();
     }
-    // D^T = W A^T: lane holds output row (lane & 15) of row block i, columns 16 j + 4 (lane >> 4) .. + 3
+    // tile_mma's fragment map: the lane holds output row (lane & 15) of row block i, columns 16 j + 4 (lane >> 4) .. + 3
 #pragma unroll
-    for (int i = 0; i < NACC; ++i) {
+    for (int i = 0; i < WM; ++i) {
         const long m = m0 + 16 * WM * wave + 16 * i + fr;
         if (m >= M) continue;
 #pragma unroll
@@ -285,15 +256,13 @@ __global__ __launch_bounds__(256) void i3d_logits_kernel(const float* pooled, co
     if (lane == 0) logits[item] = tot / (float)Tp;
 }
 
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-unsigned grid_of(long total) { const long g = (total + 255) / 256; return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536); }
 int same_out(int size, int s) { return (size + s - 1) / s; }
 
 }  // namespace
 
 extern "C" int mebt_op_i3d_conv(int32_t dtype, const mebt_i3d_conv_desc* d, mebt_stream_t stream) {
     if (!d || !d->in || !d->w) { mebt_set_error("i3d_conv: null pointer"); return MEBT_EINVAL; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("i3d_conv: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (int rc = check_dtype("i3d_conv", dtype)) return rc;
     const mebt_i3d_conv_desc& p = *d;
     if (p.B < 1 || p.Ti < 1 || p.Hi < 1 || p.Wi < 1 || p.Cin < 1 || p.Cin > 0xFFFF || p.Cout < 1) {
         mebt_set_error("i3d_conv: bad shape"); return MEBT_EINVAL;
@@ -324,12 +293,11 @@ extern "C" int mebt_op_i3d_conv(int32_t dtype, const mebt_i3d_conv_desc* d, mebt
     if ((vec_mode ? Kpad / vec : Kpad) > I3D_MAX_TAB) { mebt_set_error("i3d_conv: K too long for the LDS tap table"); return MEBT_EINVAL; }
     if ((size_t)p.B * p.Ti * p.Hi * p.Wi > 0x7FFFFFFFull) { mebt_set_error("i3d_conv: input has more than 2^31 voxels"); return MEBT_EINVAL; }
     const long M = (long)p.B * p.To * p.Ho * p.Wo;
-    const int bm = f16 ? ConvCfg<f16_t>::BM : ConvCfg<float>::BM;
+    const int bm = f16 ? TileCfg<f16_t>::BM : TileCfg<float>::BM;
     const long gx = (M + bm - 1) / bm;
     if (gx > 0x7FFFFFFFL) { mebt_set_error("i3d_conv: too many output voxels"); return MEBT_EINVAL; }
     const dim3 grid((unsigned)gx, (unsigned)((p.Cout + I3D_BN - 1) / I3D_BN));
-    if (f16) hipLaunchKernelGGL(i3d_conv_kernel<f16_t>, grid, dim3(256), 0, S(stream), p, vec_mode, Kpad);
-    else hipLaunchKernelGGL(i3d_conv_kernel<float>, grid, dim3(256), 0, S(stream), p, vec_mode, Kpad);
+    with_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(i3d_conv_kernel<decltype(tag)>, grid, dim3(256), 0, S(stream), p, vec_mode, Kpad); });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -337,7 +305,7 @@ extern "C" int mebt_op_i3d_conv(int32_t dtype, const mebt_i3d_conv_desc* d, mebt
 extern "C" int mebt_op_i3d_maxpool(int32_t dtype, const void* in, void* out, int32_t B, int32_t Ti, int32_t Hi, int32_t Wi, int32_t C,
                                    int32_t kt, int32_t kh, int32_t kw, int32_t st, int32_t sh, int32_t sw, mebt_stream_t stream) {
     if (!in || !out) { mebt_set_error("i3d_maxpool: null pointer"); return MEBT_EINVAL; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("i3d_maxpool: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (int rc = check_dtype("i3d_maxpool", dtype)) return rc;
     if (B < 1 || Ti < 1 || Hi < 1 || Wi < 1 || C < 1 || kt < 1 || kh < 1 || kw < 1 || st < 1 || sh < 1 || sw < 1) {
         mebt_set_error("i3d_maxpool: bad shape"); return MEBT_EINVAL;
     }
@@ -346,12 +314,11 @@ extern "C" int mebt_op_i3d_maxpool(int32_t dtype, const void* in, void* out, int
     const int pt = pad(Ti, kt, st) / 2, ph = pad(Hi, kh, sh) / 2, pw = pad(Wi, kw, sw) / 2;
     const int To = same_out(Ti, st), Ho = same_out(Hi, sh), Wo = same_out(Wi, sw);
     const long total = (long)B * To * Ho * Wo * C;
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(i3d_maxpool_kernel<f16_t>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const f16_t*>(in),
-                           reinterpret_cast<f16_t*>(out), B, Ti, Hi, Wi, C, To, Ho, Wo, kt, kh, kw, st, sh, sw, pt, ph, pw);
-    else
-        hipLaunchKernelGGL(i3d_maxpool_kernel<float>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const float*>(in),
-                           reinterpret_cast<float*>(out), B, Ti, Hi, Wi, C, To, Ho, Wo, kt, kh, kw, st, sh, sw, pt, ph, pw);
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(i3d_maxpool_kernel<T>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const T*>(in),
+                           reinterpret_cast<T*>(out), B, Ti, Hi, Wi, C, To, Ho, Wo, kt, kh, kw, st, sh, sw, pt, ph, pw);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -359,16 +326,15 @@ extern "C" int mebt_op_i3d_maxpool(int32_t dtype, const void* in, void* out, int
 extern "C" int mebt_op_i3d_preprocess(int32_t dtype, const uint8_t* in, void* out, int32_t N, int32_t H, int32_t W, int32_t Ho, int32_t Wo,
                                       mebt_stream_t stream) {
     if (!in || !out) { mebt_set_error("i3d_preprocess: null pointer"); return MEBT_EINVAL; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("i3d_preprocess: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (int rc = check_dtype("i3d_preprocess", dtype)) return rc;
     if (N < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) { mebt_set_error("i3d_preprocess: bad shape"); return MEBT_EINVAL; }
     const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
     const long total = (long)N * Ho * Wo;
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(i3d_preprocess_kernel<f16_t>, dim3(grid_of(total)), dim3(256), 0, S(stream), in, reinterpret_cast<f16_t*>(out), N, H, W, Ho,
-                           Wo, sy, sx);
-    else
-        hipLaunchKernelGGL(i3d_preprocess_kernel<float>, dim3(grid_of(total)), dim3(256), 0, S(stream), in, reinterpret_cast<float*>(out), N, H, W, Ho,
-                           Wo, sy, sx);
+    const dim3 grid(grid_of(total));
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(i3d_preprocess_kernel<T>, grid, dim3(256), 0, S(stream), in, reinterpret_cast<T*>(out), N, H, W, Ho, Wo, sy, sx);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -376,18 +342,17 @@ extern "C" int mebt_op_i3d_preprocess(int32_t dtype, const uint8_t* in, void* ou
 extern "C" int mebt_op_i3d_head(int32_t dtype, const void* x, const float* w, const float* bias, float* pooled, float* logits, int32_t B, int32_t T,
                                 int32_t H, int32_t W, int32_t C, int32_t ncls, mebt_stream_t stream) {
     if (!x || !w || !pooled || !logits) { mebt_set_error("i3d_head: null pointer"); return MEBT_EINVAL; }
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) { mebt_set_error("i3d_head: dtype must be f32 or f16"); return MEBT_EDTYPE; }
+    if (int rc = check_dtype("i3d_head", dtype)) return rc;
     if (B < 1 || T < 2 || H != 7 || W != 7 || C < 1 || ncls < 1) {
         mebt_set_error("i3d_head: expects [B, T >= 2, 7, 7, C] (AvgPool3d [2, 7, 7] to one spatial position)"); return MEBT_EINVAL;
     }
     const long np = (long)B * (T - 1) * C;
     const long nl = (long)B * ncls;
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(i3d_avgpool_kernel<f16_t>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, S(stream), reinterpret_cast<const f16_t*>(x),
-                           pooled, B, T, H, W, C);
-    else
-        hipLaunchKernelGGL(i3d_avgpool_kernel<float>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, S(stream), reinterpret_cast<const float*>(x),
-                           pooled, B, T, H, W, C);
+    const dim3 pool_grid((unsigned)((np + 255) / 256));
+    with_dtype(dtype, [&](auto tag) {
+        using E = decltype(tag);
+        hipLaunchKernelGGL(i3d_avgpool_kernel<E>, pool_grid, dim3(256), 0, S(stream), reinterpret_cast<const E*>(x), pooled, B, T, H, W, C);
+    });
     hipLaunchKernelGGL(i3d_logits_kernel, dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, S(stream), pooled, w, bias, logits, B, T - 1, C, ncls);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;

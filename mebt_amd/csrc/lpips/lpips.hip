@@ -16,21 +16,14 @@
 //
 // Head.  One wave per pixel: channel norms and the weighted squared difference in fp32 (at most C / 64 terms per lane between
 // fixed-order butterflies), fp64 from there; one fp64 partial per workgroup in the caller's scratch, added in index order by a
-// second kernel (csrc/recon/recon.hip's scheme: no float atomics, the same bits on every run).
-#include <cstdio>
-
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+// second kernel (csrc/block_reduce.h: no float atomics, the same bits on every run).
+#include "../block_reduce.h"
+#include "../host_util.h"
+#include "../mfma_tile.h"
 
 namespace {
 
-constexpr int CV_BK = 32, CV_BN = 64, CV_THREADS = 256;
-
-template <typename T> struct CvCfg;
-// fp16: 128 pixels x 64 channels, each wave two 16-pixel blocks, v_mfma_f32_16x16x32_f16
-template <> struct CvCfg<f16_t> { static constexpr int VEC = 8, WM = 2, BM = 128, LD = 40, NPOS_SMALL = 208; };
-// fp32: 64 pixels x 64 channels, each wave one 16-pixel block, v_mfma_f32_16x16x4_f32 (an exact fp32 FMA chain)
-template <> struct CvCfg<float> { static constexpr int VEC = 4, WM = 1, BM = 64, LD = 36, NPOS_SMALL = 128; };
+constexpr int CV_BK = TILE_BK, CV_BN = TILE_BN, CV_THREADS = TILE_THREADS;
 
 struct ConvArgs {
     const void* in; const void* w; const float* bias; void* out;
@@ -70,9 +63,12 @@ __device__ __forceinline__ void store_pixel(T* o, const f32x4* acc, int n0, int 
     }
 }
 
+// staged positions (patches with their halos) of the small-patch instantiation; the large-patch one holds 4 BM
+template <typename T> constexpr int NPOS_SMALL = sizeof(T) == 2 ? 208 : 128;
+
 template <typename T, int NPOS, bool MASK = false>
 __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
-    using Cfg = CvCfg<T>;
+    using Cfg = TileCfg<T>;
     constexpr int VEC = Cfg::VEC, LD = Cfg::LD, WM = Cfg::WM;
     constexpr int CPR = CV_BK / VEC;                                 // 16-byte chunks per 32-channel row
     constexpr int ACH = (NPOS * CPR + CV_THREADS - 1) / CV_THREADS;  // patch chunks per thread
@@ -153,10 +149,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
     };
 
     f32x4 acc[WM][4];
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    tile_zero(acc);
 
     const int nst = (p.Cin / CV_BK) * 3;                             // stages: (slice, dh)
     gloadA(0);
@@ -172,30 +165,12 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
         const int shift = (st % 3 - 1) * LW - 1;                      // window of tap (dh, 0)
 #pragma unroll
         for (int dw = 0; dw < 3; ++dw) {
-            if constexpr (sizeof(T) == 2) {
-                f16x8 af[WM], bf[4];
+            int ar[WM], br[4];
 #pragma unroll
-                for (int i = 0; i < WM; ++i) af[i] = *reinterpret_cast<const f16x8*>(&sA[(apos[i] + shift + dw) * LD + fq * 8]);
+            for (int i = 0; i < WM; ++i) ar[i] = (apos[i] + shift + dw) * LD;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(&sB[((16 * j + fr) * 3 + dw) * LD + fq * 8]);
-#pragma unroll
-                for (int i = 0; i < WM; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int q = 0; q < CV_BK / 4; ++q) {
-                    float af[WM], bf[4];
-#pragma unroll
-                    for (int i = 0; i < WM; ++i) af[i] = sA[(apos[i] + shift + dw) * LD + 4 * q + fq];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) bf[j] = sB[((16 * j + fr) * 3 + dw) * LD + 4 * q + fq];
-#pragma unroll
-                    for (int i = 0; i < WM; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j], af[i], acc[i][j], 0, 0, 0);
-                }
-            }
+            for (int j = 0; j < 4; ++j) br[j] = ((16 * j + fr) * 3 + dw) * LD;
+            tile_mma<T, WM>(acc, sA, ar, sB, br, fq);
         }
         __syncthreads();
         if (more) lstoreB();
@@ -203,7 +178,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
         __syncthreads();
     }
 
-    // D^T = W A^T: the lane holds pixel (lane & 15) of block i, channels 16 j + 4 (lane >> 4) .. + 3
+    // tile_mma's fragment map: the lane holds pixel (lane & 15) of block i, channels 16 j + 4 (lane >> 4) .. + 3
     T* out = reinterpret_cast<T*>(p.out);
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_kernel(const ConvArgs p) {
 // Cin = 3: rows are the flat (image, pixel) index; the 27 taps x channels of a row are gathered into one K step
 template <typename T>
 __global__ __launch_bounds__(CV_THREADS) void conv3x3_c3_kernel(const ConvArgs p, long long M) {
-    using Cfg = CvCfg<T>;
+    using Cfg = TileCfg<T>;
     constexpr int VEC = Cfg::VEC, BM = Cfg::BM, LD = Cfg::LD, WM = Cfg::WM;
     constexpr int CPR = CV_BK / VEC;
     __shared__ __attribute__((aligned(16))) T sA[BM * LD];
@@ -267,35 +242,14 @@ __global__ __launch_bounds__(CV_THREADS) void conv3x3_c3_kernel(const ConvArgs p
     __syncthreads();
 
     f32x4 acc[WM][4];
+    tile_zero(acc);
+    int ar[WM], br[4];
 #pragma unroll
-    for (int i = 0; i < WM; ++i)
+    for (int i = 0; i < WM; ++i) ar[i] = (16 * WM * wave + 16 * i + fr) * LD;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (sizeof(T) == 2) {
-        f16x8 af[WM], bf[4];
-#pragma unroll
-        for (int i = 0; i < WM; ++i) af[i] = *reinterpret_cast<const f16x8*>(&sA[(16 * WM * wave + 16 * i + fr) * LD + fq * 8]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bf[j] = *reinterpret_cast<const f16x8*>(&sB[(16 * j + fr) * LD + fq * 8]);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int q = 0; q < CV_BK / 4; ++q) {
-            float af[WM], bf[4];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) af[i] = sA[(16 * WM * wave + 16 * i + fr) * LD + 4 * q + fq];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bf[j] = sB[(16 * j + fr) * LD + 4 * q + fq];
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bf[j], af[i], acc[i][j], 0, 0, 0);
-        }
-    }
-    T* out = reinterpret_cast<T*>(p.out);
+    for (int j = 0; j < 4; ++j) br[j] = (16 * j + fr) * LD;
+    tile_mma<T, WM>(acc, sA, ar, sB, br, fq);
+    T* out = reinterpret_cast<T*>(p.out);                           // tile_mma's fragment map: the lane holds row (lane & 15) of block i
 #pragma unroll
     for (int i = 0; i < WM; ++i) {
         const long long pix = s_pix[16 * WM * wave + 16 * i + fr];
@@ -376,57 +330,31 @@ __global__ __launch_bounds__(HD_THREADS) void lpips_head_kernel(const T* __restr
             const float d = (float)a[c] / d0 - (float)b[c] / d1;
             t += w[c] * (d * d);
         }
-        double rs = (double)t;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
-        acc += rs;
+        acc += wave_sum((double)t);
     }
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    const double s = waves_sum<HD_WAVES>(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// out[n] += v, layer_out[n * layer_stride] = v, v = inv_p * (part[n * blocks + 0] + part[n * blocks + 1] + ...): lane t adds slots
-// t, t + 256, ... in order, then the lanes by butterfly and the waves in turn
+// out[n] += v, layer_out[n * layer_stride] = v, v = inv_p * (part[n * blocks + 0] + part[n * blocks + 1] + ...), the slots in
+// slot_sum's order
 __global__ __launch_bounds__(HD_THREADS) void lpips_head_finish_kernel(const double* __restrict__ part, long long blocks, double* __restrict__ out,
                                                                        double* __restrict__ layer_out, long long layer_stride, double inv_p) {
     __shared__ double sh[HD_WAVES];
-    const double* p = part + (size_t)blockIdx.x * (size_t)blocks;
-    double v = 0.0;
-    for (long long j = threadIdx.x; j < blocks; j += HD_THREADS) v += p[j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
+    const double v = slot_sum<HD_THREADS>(part + (size_t)blockIdx.x * (size_t)blocks, blocks, sh);
     if (threadIdx.x == 0) {
         // the product is rounded before it is added (no fused multiply-add): out accumulates exactly the values layer_out receives
 #pragma clang fp contract(off)
-        const double s = (((sh[0] + sh[1]) + sh[2]) + sh[3]) * inv_p;
+        const double s = v * inv_p;
         out[blockIdx.x] = out[blockIdx.x] + s;
         if (layer_out) layer_out[(size_t)blockIdx.x * (size_t)layer_stride] = s;
     }
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-unsigned grid_of(long long total) { const long long g = (total + 255) / 256; return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536); }
-
-int fail(int code, const char* who, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    mebt_set_error(msg);
-    return code;
-}
-
-int check_dtype(const char* who, int32_t dtype) {
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) return fail(MEBT_EDTYPE, who, "dtype must be f32 or f16");
-    return MEBT_OK;
-}
-
 template <typename T, bool MASK = false>
 int launch_conv(ConvArgs a, hipStream_t stream) {
-    using Cfg = CvCfg<T>;
+    using Cfg = TileCfg<T>;
     const unsigned gy = (unsigned)((a.Cout + CV_BN - 1) / CV_BN);
     if (!MASK && a.Cin == 3) {
         const long long M = (long long)a.N * a.H * a.W, gx = (M + Cfg::BM - 1) / Cfg::BM;
@@ -446,7 +374,7 @@ int launch_conv(ConvArgs a, hipStream_t stream) {
     if (gx > 0x7FFFFFFFll) return fail(MEBT_ESHAPE, "conv2d_3x3", "too many output pixels for one launch");
     const int npos = a.G * (ph + 2) * (pw + 2);                     // <= 4 BM
     const dim3 grid((unsigned)gx, gy);
-    if (npos <= Cfg::NPOS_SMALL) hipLaunchKernelGGL((conv3x3_kernel<T, Cfg::NPOS_SMALL, MASK>), grid, dim3(CV_THREADS), 0, stream, a);
+    if (npos <= NPOS_SMALL<T>) hipLaunchKernelGGL((conv3x3_kernel<T, NPOS_SMALL<T>, MASK>), grid, dim3(CV_THREADS), 0, stream, a);
     else hipLaunchKernelGGL((conv3x3_kernel<T, 4 * Cfg::BM, MASK>), grid, dim3(CV_THREADS), 0, stream, a);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
@@ -468,12 +396,11 @@ extern "C" int mebt_op_lpips_input(int32_t dtype, const float* video, const int3
         if (!(scale[c] != 0.f)) return fail(MEBT_EINVAL, who, "scale must be non-zero");
     }
     const long long total = (long long)n_frames * H * W;
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(lpips_input_kernel<f16_t>, dim3(grid_of(total)), dim3(256), 0, S(stream), video, frames, reinterpret_cast<f16_t*>(out), B,
-                           T, H, W, total, sc);
-    else
-        hipLaunchKernelGGL(lpips_input_kernel<float>, dim3(grid_of(total)), dim3(256), 0, S(stream), video, frames, reinterpret_cast<float*>(out), B,
-                           T, H, W, total, sc);
+    with_dtype(dtype, [&](auto tag) {
+        using E = decltype(tag);
+        hipLaunchKernelGGL(lpips_input_kernel<E>, dim3(grid_of(total)), dim3(256), 0, S(stream), video, frames, reinterpret_cast<E*>(out), B, T, H, W,
+                           total, sc);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -491,7 +418,7 @@ extern "C" int mebt_op_conv2d_3x3(int32_t dtype, const void* in, const void* w, 
     a.in = in; a.w = w; a.bias = bias; a.out = out;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu != 0;
     a.Kpad = (9 * Cin + CV_BK - 1) / CV_BK * CV_BK;
-    return dtype == MEBT_DTYPE_F16 ? launch_conv<f16_t>(a, S(stream)) : launch_conv<float>(a, S(stream));
+    return with_dtype(dtype, [&](auto tag) { return launch_conv<decltype(tag)>(a, S(stream)); });
 }
 
 // The data gradient of the convolution above: the same kernel on `arrange_weight_dgrad`'s weights (taps flipped, channels swapped),
@@ -510,9 +437,9 @@ extern "C" int mebt_op_conv2d_3x3_dgrad(int32_t dtype, const void* dy, const voi
     a.in = dy; a.w = w_dgrad; a.bias = nullptr; a.out = dx; a.mask = y_prev;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = 0;
     a.Kpad = (9 * Cin + CV_BK - 1) / CV_BK * CV_BK;
-    const bool f16 = dtype == MEBT_DTYPE_F16;
-    if (y_prev) return f16 ? launch_conv<f16_t, true>(a, S(stream)) : launch_conv<float, true>(a, S(stream));
-    return f16 ? launch_conv<f16_t>(a, S(stream)) : launch_conv<float>(a, S(stream));
+    return with_dtype(dtype, [&](auto tag) {
+        return y_prev ? launch_conv<decltype(tag), true>(a, S(stream)) : launch_conv<decltype(tag)>(a, S(stream));
+    });
 }
 
 extern "C" int mebt_op_maxpool_2x2(int32_t dtype, const void* in, void* out, int32_t N, int32_t H, int32_t W, int32_t C, mebt_stream_t stream) {
@@ -522,23 +449,17 @@ extern "C" int mebt_op_maxpool_2x2(int32_t dtype, const void* in, void* out, int
     if (N < 1 || C < 1) return fail(MEBT_ESHAPE, who, "need N, C >= 1");
     if (H < 2 || W < 2) return fail(MEBT_ESHAPE, who, "a 2 x 2 window needs H >= 2 and W >= 2");
     const int Ho = H / 2, Wo = W / 2;
-    const bool f16 = dtype == MEBT_DTYPE_F16;
-    const int vec = f16 ? 8 : 4;
+    const int vec = dtype == MEBT_DTYPE_F16 ? 8 : 4;
     const bool wide = C % vec == 0 && aligned16(in) && aligned16(out);
     const long long total = (long long)N * Ho * Wo * (wide ? C / vec : C);
     const dim3 grid(grid_of(total)), block(256);
-    if (f16 && wide)
-        hipLaunchKernelGGL((maxpool2x2_kernel<f16_t, 8>), grid, block, 0, S(stream), reinterpret_cast<const f16_t*>(in), reinterpret_cast<f16_t*>(out),
-                           H, W, C, Ho, Wo, total);
-    else if (f16)
-        hipLaunchKernelGGL((maxpool2x2_kernel<f16_t, 1>), grid, block, 0, S(stream), reinterpret_cast<const f16_t*>(in), reinterpret_cast<f16_t*>(out),
-                           H, W, C, Ho, Wo, total);
-    else if (wide)
-        hipLaunchKernelGGL((maxpool2x2_kernel<float, 4>), grid, block, 0, S(stream), reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out),
-                           H, W, C, Ho, Wo, total);
-    else
-        hipLaunchKernelGGL((maxpool2x2_kernel<float, 1>), grid, block, 0, S(stream), reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out),
-                           H, W, C, Ho, Wo, total);
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const T* i = reinterpret_cast<const T*>(in);
+        T* o = reinterpret_cast<T*>(out);
+        if (wide) hipLaunchKernelGGL((maxpool2x2_kernel<T, 16 / sizeof(T)>), grid, block, 0, S(stream), i, o, H, W, C, Ho, Wo, total);
+        else hipLaunchKernelGGL((maxpool2x2_kernel<T, 1>), grid, block, 0, S(stream), i, o, H, W, C, Ho, Wo, total);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -551,18 +472,15 @@ extern "C" int mebt_op_lpips_head(int32_t dtype, const void* feats, const float*
     if (N < 1 || P < 1 || C < 1 || P > (1ll << 40)) return fail(MEBT_ESHAPE, who, "need N, C >= 1 and 1 <= P <= 2^40");
     if (layer_out && layer_stride < 1) return fail(MEBT_EINVAL, who, "layer_stride must be >= 1");
     const long long blocks = (P + HD_ROWS - 1) / HD_ROWS;
-    if (N > 0x7FFFFFFFll / blocks) return fail(MEBT_ESHAPE, who, "too large for one launch");
-    if (!scratch) return fail(MEBT_EINVAL, who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(scratch) & 7) return fail(MEBT_EINVAL, who, "scratch must be 8-byte aligned");
-    if (scratch_bytes < 8 * N * blocks) return fail(MEBT_EWORKSPACE, who, "scratch too small");
+    if (N > 0x7FFFFFFFll / blocks) return fail(MEBT_ESHAPE, who, "too large for one launch");           // before N * blocks can overflow
+    if (int rc = check_scratch(who, scratch, scratch_bytes, 8 * N * blocks, N * blocks)) return rc;
     double* part = reinterpret_cast<double*>(scratch);
     const dim3 grid((unsigned)(N * blocks));
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(lpips_head_kernel<f16_t>, grid, dim3(HD_THREADS), 0, S(stream), reinterpret_cast<const f16_t*>(feats), w, part,
-                           (long long)N, (long long)P, C, blocks);
-    else
-        hipLaunchKernelGGL(lpips_head_kernel<float>, grid, dim3(HD_THREADS), 0, S(stream), reinterpret_cast<const float*>(feats), w, part,
-                           (long long)N, (long long)P, C, blocks);
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(lpips_head_kernel<T>, grid, dim3(HD_THREADS), 0, S(stream), reinterpret_cast<const T*>(feats), w, part, (long long)N,
+                           (long long)P, C, blocks);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(lpips_head_finish_kernel, dim3((unsigned)N), dim3(HD_THREADS), 0, S(stream), part, blocks, out, layer_out,
                        (long long)layer_stride, 1.0 / (double)P);

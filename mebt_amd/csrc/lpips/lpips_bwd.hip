@@ -5,11 +5,9 @@
 // every offset is 64-bit.  Nothing here adds into memory another thread writes and no reduction crosses a wave, so every run gives the
 // same bits and an image's gradient does not depend on the batch it ran in.
 #include <algorithm>
-#include <cstdio>
 #include <vector>
 
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+#include "../host_util.h"
 
 namespace {
 
@@ -129,23 +127,6 @@ __global__ __launch_bounds__(256) void lpips_input_bwd_kernel(const T* __restric
     }
 }
 
-// ---- host side -------------------------------------------------------------------------------------------------------------------------
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-unsigned grid_of(long long total) { const long long g = (total + 255) / 256; return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536); }
-
-int fail(int code, const char* who, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    mebt_set_error(msg);
-    return code;
-}
-
-int check_dtype(const char* who, int32_t dtype) {
-    if (dtype != MEBT_DTYPE_F32 && dtype != MEBT_DTYPE_F16) return fail(MEBT_EDTYPE, who, "dtype must be f32 or f16");
-    return MEBT_OK;
-}
-
 }  // namespace
 
 extern "C" int mebt_op_lpips_head_bwd(int32_t dtype, const void* feats, const float* w, const void* add, void* d_feats, int64_t N, int64_t P,
@@ -159,12 +140,11 @@ extern "C" int mebt_op_lpips_head_bwd(int32_t dtype, const void* feats, const fl
     if (!(k == k) || k - k != 0.f) return fail(MEBT_EINVAL, who, "coef / P must be finite in fp32");
     const long long rows = (long long)N * P, g = (rows + HB_WAVES - 1) / HB_WAVES;
     const dim3 grid((unsigned)(g < 65536 ? g : 65536));
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(lpips_head_bwd_kernel<f16_t>, grid, dim3(HB_THREADS), 0, S(stream), reinterpret_cast<const f16_t*>(feats), w,
-                           reinterpret_cast<const f16_t*>(add), reinterpret_cast<f16_t*>(d_feats), (long long)N, (long long)P, C, k, rows);
-    else
-        hipLaunchKernelGGL(lpips_head_bwd_kernel<float>, grid, dim3(HB_THREADS), 0, S(stream), reinterpret_cast<const float*>(feats), w,
-                           reinterpret_cast<const float*>(add), reinterpret_cast<float*>(d_feats), (long long)N, (long long)P, C, k, rows);
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(lpips_head_bwd_kernel<T>, grid, dim3(HB_THREADS), 0, S(stream), reinterpret_cast<const T*>(feats), w,
+                           reinterpret_cast<const T*>(add), reinterpret_cast<T*>(d_feats), (long long)N, (long long)P, C, k, rows);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -177,23 +157,18 @@ extern "C" int mebt_op_maxpool_2x2_bwd(int32_t dtype, const void* in, const void
     if (N < 1 || C < 1) return fail(MEBT_ESHAPE, who, "need N, C >= 1");
     if (H < 2 || W < 2) return fail(MEBT_ESHAPE, who, "a 2 x 2 window needs H >= 2 and W >= 2");
     const int Ho = H / 2, Wo = W / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
-    const bool f16 = dtype == MEBT_DTYPE_F16;
-    const int vec = f16 ? 8 : 4;
+    const int vec = dtype == MEBT_DTYPE_F16 ? 8 : 4;
     const bool wide = C % vec == 0 && aligned16(in) && aligned16(dy) && aligned16(dx);
     const long long total = (long long)N * Hc * Wc * (wide ? C / vec : C);
     const dim3 grid(grid_of(total)), block(256);
-    if (f16 && wide)
-        hipLaunchKernelGGL((maxpool2x2_bwd_kernel<f16_t, 8>), grid, block, 0, S(stream), reinterpret_cast<const f16_t*>(in),
-                           reinterpret_cast<const f16_t*>(dy), reinterpret_cast<f16_t*>(dx), H, W, C, Ho, Wo, Hc, Wc, total);
-    else if (f16)
-        hipLaunchKernelGGL((maxpool2x2_bwd_kernel<f16_t, 1>), grid, block, 0, S(stream), reinterpret_cast<const f16_t*>(in),
-                           reinterpret_cast<const f16_t*>(dy), reinterpret_cast<f16_t*>(dx), H, W, C, Ho, Wo, Hc, Wc, total);
-    else if (wide)
-        hipLaunchKernelGGL((maxpool2x2_bwd_kernel<float, 4>), grid, block, 0, S(stream), reinterpret_cast<const float*>(in),
-                           reinterpret_cast<const float*>(dy), reinterpret_cast<float*>(dx), H, W, C, Ho, Wo, Hc, Wc, total);
-    else
-        hipLaunchKernelGGL((maxpool2x2_bwd_kernel<float, 1>), grid, block, 0, S(stream), reinterpret_cast<const float*>(in),
-                           reinterpret_cast<const float*>(dy), reinterpret_cast<float*>(dx), H, W, C, Ho, Wo, Hc, Wc, total);
+    with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const T* i = reinterpret_cast<const T*>(in);
+        const T* g = reinterpret_cast<const T*>(dy);
+        T* o = reinterpret_cast<T*>(dx);
+        if (wide) hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T, 16 / sizeof(T)>), grid, block, 0, S(stream), i, g, o, H, W, C, Ho, Wo, Hc, Wc, total);
+        else hipLaunchKernelGGL((maxpool2x2_bwd_kernel<T, 1>), grid, block, 0, S(stream), i, g, o, H, W, C, Ho, Wo, Hc, Wc, total);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -225,12 +200,11 @@ extern "C" int mebt_op_lpips_input_bwd(int32_t dtype, const void* d_in, const in
     if (std::adjacent_find(keys.begin(), keys.end()) != keys.end())
         return fail(MEBT_EINVAL, who, "the (b, t) pairs must be distinct: each seed element has one writer");
     const long long total = (long long)n_frames * H * W;
-    if (dtype == MEBT_DTYPE_F16)
-        hipLaunchKernelGGL(lpips_input_bwd_kernel<f16_t>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const f16_t*>(d_in), frames,
-                           seed, T, H, W, total, factor, sc);
-    else
-        hipLaunchKernelGGL(lpips_input_bwd_kernel<float>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const float*>(d_in), frames,
-                           seed, T, H, W, total, factor, sc);
+    with_dtype(dtype, [&](auto tag) {
+        using E = decltype(tag);
+        hipLaunchKernelGGL(lpips_input_bwd_kernel<E>, dim3(grid_of(total)), dim3(256), 0, S(stream), reinterpret_cast<const E*>(d_in), frames, seed,
+                           T, H, W, total, factor, sc);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

@@ -7,10 +7,9 @@
 // slots of each output in index order.  The same input therefore gives the same bits on every run.  The only atomics are the 64-bit
 // integer adds of the code histogram, which are exact in any order.  Every offset into an operand is 64-bit.
 #include <cmath>
-#include <cstdio>
 
-#include "../common.h"
-#include "../../../include/mebt_hip.h"
+#include "../block_reduce.h"
+#include "../host_util.h"
 
 namespace {
 
@@ -19,28 +18,11 @@ struct SsimWindow { float g[11]; };                  // the normalised 11-tap Ga
 constexpr int RC_THREADS = 256;
 constexpr int RC_WAVES = RC_THREADS / MEBT_WAVE;
 
-// the workgroup's sum in a fixed order, returned to every thread; `sh` [RC_WAVES] may be reused afterwards
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = sh[0];
-#pragma unroll
-    for (int w = 1; w < RC_WAVES; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
-
-// out[o] = scale * (part[o * count + 0] + part[o * count + 1] + ...): lane t takes slots t, t + 256, ... in order, then block_sum
+// out[o] = scale * (part[o * count + 0] + part[o * count + 1] + ...), the slots in slot_sum's order
 __global__ __launch_bounds__(RC_THREADS) void sum_partials_kernel(const double* __restrict__ part, int64_t count, double* __restrict__ out,
                                                                   double scale) {
     __shared__ double sh[RC_WAVES];
-    const double* p = part + (size_t)blockIdx.x * (size_t)count;
-    double acc = 0.0;
-    for (int64_t j = threadIdx.x; j < count; j += RC_THREADS) acc += p[j];
-    const double s = block_sum(acc, sh);
+    const double s = slot_sum<RC_THREADS>(part + (size_t)blockIdx.x * (size_t)count, count, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = s * scale;
 }
 
@@ -72,7 +54,7 @@ __global__ __launch_bounds__(RC_THREADS) void abs_diff_kernel(const float* __res
     } else {
         for (int64_t i = c0 + threadIdx.x; i < c1; i += RC_THREADS) acc += fabsf(xb[i] - yb[i]);
     }
-    const double s = block_sum((double)acc, sh);
+    const double s = block_sum<RC_WAVES>((double)acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -171,8 +153,8 @@ __global__ __launch_bounds__(RC_THREADS) void clip_quality_kernel(const uint8_t*
         }
         __syncthreads();
     }
-    const double s = block_sum(acc, sh_d);
-    const long long q = block_sum((long long)sq, sh_q);
+    const double s = block_sum<RC_WAVES>(acc, sh_d);
+    const long long q = block_sum<RC_WAVES>((long long)sq, sh_q);
     if (tid == 0) {
         part_ssim[blockIdx.x] = s;
         part_sq[blockIdx.x] = q;
@@ -192,8 +174,8 @@ __global__ __launch_bounds__(RC_THREADS) void clip_quality_finish_kernel(const d
         acc += part_ssim[base + j];
         q += part_sq[base + j];
     }
-    const double s = block_sum(acc, sh_d);
-    q = block_sum(q, sh_q);
+    const double s = block_sum<RC_WAVES>(acc, sh_d);
+    q = block_sum<RC_WAVES>(q, sh_q);
     if (threadIdx.x == 0) {
         ssim[blockIdx.x] = s * inv_count;
         sq_err[blockIdx.x] = (int64_t)q;
@@ -232,18 +214,12 @@ __global__ __launch_bounds__(RC_THREADS) void code_stats_kernel(const int64_t* _
                 rs += (double)(t0 * t0);
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
-        acc += rs;
+        acc += wave_sum(rs);
         if (lane == 0) atomicAdd(hist + id, 1ull);
     }
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    const double s = waves_sum<RC_WAVES>(acc, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-hipStream_t S(mebt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- workgroup counts (the scratch formulas of the header) and launchers, which trust their arguments: the entry points check them ------
 int64_t recon_abs_diff_blocks(int64_t n) { return (n + ABS_CHUNK - 1) / ABS_CHUNK; }
@@ -289,23 +265,6 @@ int launch_code_stats(const int64_t* ids, const float* z, const float* emb, int6
     MEBT_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(RC_THREADS), 0, stream, scratch, blocks, sq_sum, 1.0);
     MEBT_HIP_CHECK(hipGetLastError());
-    return MEBT_OK;
-}
-
-// ---- argument checks -------------------------------------------------------------------------------------------------------------------
-int fail(int code, const char* who, const char* what) {
-    char msg[160];
-    snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    mebt_set_error(msg);
-    return code;
-}
-
-// the slab must hold `need` bytes and start on an 8-byte boundary; the workgroups of one launch stay below 2^31
-int check_scratch(const char* who, const void* scratch, int64_t scratch_bytes, int64_t need, int64_t blocks) {
-    if (blocks > 0x7FFFFFFFll) return fail(MEBT_ESHAPE, who, "too large for one launch");
-    if (!scratch) return fail(MEBT_EINVAL, who, "null pointer");
-    if (reinterpret_cast<uintptr_t>(scratch) & 7) return fail(MEBT_EINVAL, who, "scratch must be 8-byte aligned");
-    if (scratch_bytes < need) return fail(MEBT_EWORKSPACE, who, "scratch too small");
     return MEBT_OK;
 }
 

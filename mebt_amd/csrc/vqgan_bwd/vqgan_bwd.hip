@@ -352,8 +352,9 @@ extern "C" int mebt_op_pad_zero(int32_t dtype, const void* src, void* dst, int32
     if (!total) return MEBT_OK;
     if (!dst || (!src && (size_t)B * T * H * W * C)) { mebt_set_error("pad_zero: null pointer"); return MEBT_EINVAL; }
     const unsigned blocks = blocks_for(total, 65536);
-    if (is_f16(dtype)) hipLaunchKernelGGL(pad_zero_kernel<f16_t>, dim3(blocks), dim3(256), 0, S(stream), src, (f16_t*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
-    else hipLaunchKernelGGL(pad_zero_kernel<float>, dim3(blocks), dim3(256), 0, S(stream), src, (float*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
+    with_dtype(dtype, [&](auto tag) {
+        hipLaunchKernelGGL(pad_zero_kernel<decltype(tag)>, dim3(blocks), dim3(256), 0, S(stream), src, (decltype(tag)*)dst, T, H, W, fT, fH, fW, pT, pH, pW, C, src_mode, (long)total);
+    });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }
@@ -407,8 +408,7 @@ extern "C" int mebt_op_conv3d_wgrad(int32_t dtype, const mebt_conv3d_desc* d, fl
     if ((long)co_tiles * ci_tiles > 65535) { mebt_set_error("conv3d_wgrad: too many channel tiles"); return MEBT_ESHAPE; }
     const dim3 grid(ns, p.ntaps, co_tiles * ci_tiles);
     float* part = reinterpret_cast<float*>(scratch);
-    if (is_f16(dtype)) hipLaunchKernelGGL(conv3d_wgrad_kernel<f16_t>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride);
-    else hipLaunchKernelGGL(conv3d_wgrad_kernel<float>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride);
+    with_dtype(dtype, [&](auto tag) { hipLaunchKernelGGL(conv3d_wgrad_kernel<decltype(tag)>, grid, dim3(256), 0, S(stream), p, part, chunk, ci_tiles, stride); });
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, S(stream), part, dw, db, nw, stride, ns, inv_scale);
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
@@ -447,8 +447,7 @@ extern "C" int mebt_op_groupnorm_silu_bwd(int32_t dtype, const void* x, const fl
         hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, S(stream), part, dgamma, dbeta, B, nslab, C, inv_scale);
         hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ablocks), dim3(256), 0, S(stream), xt, dyt, addt, dxt, stats, gs, gamma, beta, (long)vox_per_sample, C, total4);
     };
-    if (is_f16(dtype)) run((const f16_t*)x, (const f16_t*)dy, (const f16_t*)add, (f16_t*)dx);
-    else run((const float*)x, (const float*)dy, (const float*)add, (float*)dx);
+    with_dtype(dtype, [&](auto tag) { using E = decltype(tag); run((const E*)x, (const E*)dy, (const E*)add, (E*)dx); });
     MEBT_HIP_CHECK(hipGetLastError());
     return MEBT_OK;
 }

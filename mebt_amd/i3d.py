@@ -267,7 +267,7 @@ class InceptionI3d(nn.Module):
         return prep
 
     def _tdt(self):
-        return torch.float16 if self.compute_dtype == "f16" else torch.float32
+        return _lib.torch_dtype(self.compute_dtype)
 
     # ---- operators --------------------------------------------------------------------------------------------------------
     def _pool(self, x, B, dims, k, s):
@@ -277,7 +277,7 @@ class InceptionI3d(nn.Module):
         return out, od
 
     def _code(self):
-        return _lib.F16 if self.compute_dtype == "f16" else _lib.F32
+        return _lib.dtype_code(self.compute_dtype)
 
     def _unit(self, cv, x, B, dims):
         g = conv_geometry(dims, cv.k, cv.s)

@@ -149,20 +149,12 @@ def plan_flops(H, W, n_images=1):
     return sum(p[-1] for p in per), per
 
 
-def _code(dtype):
-    return _lib.F16 if dtype == "f16" else _lib.F32
-
-
-def _tdt(dtype):
-    return torch.float16 if dtype == "f16" else torch.float32
-
-
 # ---- operators (device) --------------------------------------------------------------------------------------------------------------------
 def lpips_input(video, frames, out, shift=SHIFT, scale=SCALE, dtype="f16"):
     """video fp32 [B, 3, T, H, W], frames int32 [n, 2] of (b, t) on the device, out [n, H, W, 3] of the compute dtype (written)"""
     B, _, T, H, W = video.shape
     sh, sc = (C.c_float * 3)(*[float(v) for v in shift]), (C.c_float * 3)(*[float(v) for v in scale])
-    _lib.check(_lib.load().mebt_op_lpips_input(_code(dtype), _lib.ptr(video), _lib.ptr(frames), _lib.ptr(out), B, T, H, W, int(frames.shape[0]),
+    _lib.check(_lib.load().mebt_op_lpips_input(_lib.dtype_code(dtype), _lib.ptr(video), _lib.ptr(frames), _lib.ptr(out), B, T, H, W, int(frames.shape[0]),
                                                sh, sc, _lib.cur_stream()))
     return out
 
@@ -170,7 +162,7 @@ def lpips_input(video, frames, out, shift=SHIFT, scale=SCALE, dtype="f16"):
 def conv2d_3x3(x, w, bias, out, cin, cout, dtype="f16", relu=True):
     """x [N, H, W, cin] -> out [N, H, W, cout] (written); w from `arrange_weight`, bias fp32 [cout] or None"""
     N, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
-    _lib.check(_lib.load().mebt_op_conv2d_3x3(_code(dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), N, H, W, cin, cout, int(relu),
+    _lib.check(_lib.load().mebt_op_conv2d_3x3(_lib.dtype_code(dtype), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(out), N, H, W, cin, cout, int(relu),
                                               _lib.cur_stream()))
     return out
 
@@ -187,7 +179,7 @@ def conv2d_3x3_i3d(x, w, bias, out, cin, cout, dtype="f16", relu=True):
 def maxpool_2x2(x, out, dtype="f16"):
     """x [N, H, W, C] -> out [N, H // 2, W // 2, C] (written)"""
     N, H, W, Cc = (int(v) for v in x.shape)
-    _lib.check(_lib.load().mebt_op_maxpool_2x2(_code(dtype), _lib.ptr(x), _lib.ptr(out), N, H, W, Cc, _lib.cur_stream()))
+    _lib.check(_lib.load().mebt_op_maxpool_2x2(_lib.dtype_code(dtype), _lib.ptr(x), _lib.ptr(out), N, H, W, Cc, _lib.cur_stream()))
     return out
 
 
@@ -198,7 +190,7 @@ def head_scratch_bytes(n_pairs, P):
 def lpips_head(feats, w, out, n_pairs, P, Cc, scratch, layer_out=None, layer_stride=1, dtype="f16"):
     """feats [2 n_pairs, P, Cc]; out float64 [n_pairs] += the slice's term; layer_out (a view whose element n sits n * layer_stride
     doubles on) receives the term itself"""
-    _lib.check(_lib.load().mebt_op_lpips_head(_code(dtype), _lib.ptr(feats), _lib.ptr(w), _lib.ptr(out), _lib.ptr(layer_out), layer_stride, n_pairs,
+    _lib.check(_lib.load().mebt_op_lpips_head(_lib.dtype_code(dtype), _lib.ptr(feats), _lib.ptr(w), _lib.ptr(out), _lib.ptr(layer_out), layer_stride, n_pairs,
                                               P, Cc, _lib.ptr(scratch), scratch.numel() * scratch.element_size(), _lib.cur_stream()))
     return out
 
@@ -206,7 +198,7 @@ def lpips_head(feats, w, out, n_pairs, P, Cc, scratch, layer_out=None, layer_str
 def lpips_head_bwd(feats, w, d_feats, n_pairs, P, Cc, coef, add=None, dtype="f16"):
     """feats [2 n_pairs, P, Cc] -> d_feats [n_pairs, P, Cc] (written): coef * d(slice term)/d(reconstruction features) + add, masked with
     the features' sign (include/mebt_hip.h)"""
-    _lib.check(_lib.load().mebt_op_lpips_head_bwd(_code(dtype), _lib.ptr(feats), _lib.ptr(w), _lib.ptr(add), _lib.ptr(d_feats), n_pairs, P, Cc,
+    _lib.check(_lib.load().mebt_op_lpips_head_bwd(_lib.dtype_code(dtype), _lib.ptr(feats), _lib.ptr(w), _lib.ptr(add), _lib.ptr(d_feats), n_pairs, P, Cc,
                                                   float(coef), _lib.cur_stream()))
     return d_feats
 
@@ -214,7 +206,7 @@ def lpips_head_bwd(feats, w, d_feats, n_pairs, P, Cc, coef, add=None, dtype="f16
 def maxpool_2x2_bwd(x, dy, dx, dtype="f16"):
     """x [N, H, W, C] (the pool's input), dy [N, H // 2, W // 2, C] -> dx [N, H, W, C] (every element written)"""
     N, H, W, Cc = (int(v) for v in x.shape)
-    _lib.check(_lib.load().mebt_op_maxpool_2x2_bwd(_code(dtype), _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dx), N, H, W, Cc, _lib.cur_stream()))
+    _lib.check(_lib.load().mebt_op_maxpool_2x2_bwd(_lib.dtype_code(dtype), _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dx), N, H, W, Cc, _lib.cur_stream()))
     return dx
 
 
@@ -222,7 +214,7 @@ def conv2d_3x3_dgrad(dy, w_dgrad, y_prev, dx, cin, cout, dtype="f16"):
     """dy [N, H, W, cin] (cin: the forward's Cout) -> dx [N, H, W, cout] (written), kept where y_prev > 0 when y_prev is given;
     w_dgrad from `arrange_weight_dgrad`"""
     N, H, W = int(dy.shape[0]), int(dy.shape[1]), int(dy.shape[2])
-    _lib.check(_lib.load().mebt_op_conv2d_3x3_dgrad(_code(dtype), _lib.ptr(dy), _lib.ptr(w_dgrad), _lib.ptr(y_prev), _lib.ptr(dx), N, H, W, cin, cout,
+    _lib.check(_lib.load().mebt_op_conv2d_3x3_dgrad(_lib.dtype_code(dtype), _lib.ptr(dy), _lib.ptr(w_dgrad), _lib.ptr(y_prev), _lib.ptr(dx), N, H, W, cin, cout,
                                                     _lib.cur_stream()))
     return dx
 
@@ -233,7 +225,7 @@ def lpips_input_bwd(d_in, frames, frames_host, seed, scale=SCALE, factor=1.0, dt
     B, _, T, H, W = (int(v) for v in seed.shape)
     fh = frames_host.to(torch.int32).contiguous()
     sc = (C.c_float * 3)(*[float(v) for v in scale])
-    _lib.check(_lib.load().mebt_op_lpips_input_bwd(_code(dtype), _lib.ptr(d_in), _lib.ptr(frames), C.c_void_p(fh.data_ptr()), _lib.ptr(seed), B, T, H,
+    _lib.check(_lib.load().mebt_op_lpips_input_bwd(_lib.dtype_code(dtype), _lib.ptr(d_in), _lib.ptr(frames), C.c_void_p(fh.data_ptr()), _lib.ptr(seed), B, T, H,
                                                    W, int(fh.shape[0]), sc, float(factor), _lib.cur_stream()))
     return seed
 
@@ -254,7 +246,7 @@ class LPIPS:
             raise ValueError(f"MEBT_LPIPS_CONV must be 'own' or 'i3d', not {route!r}")
         self.dtype, self.device, self.route = dtype, device, route
         self.budget_bytes = 1 << 30           # live activations of one chunk (two ping-pong buffers + the head's scratch)
-        tdt = _tdt(dtype)
+        tdt = _lib.torch_dtype(dtype)
         self.convs = []                       # (arranged weight, bias, Cin, Cout) in forward order
         for stem, cin, cout in conv_keys():
             self.convs.append((arrange_weight(sd[stem + ".weight"].to(device), tdt), sd[stem + ".bias"].to(device, torch.float32).contiguous(),
@@ -353,7 +345,7 @@ class LPIPS:
         out = torch.zeros(n, device=self.device, dtype=torch.float64)
         lay = torch.zeros(n, 5, device=self.device, dtype=torch.float64) if layers else None
         per = min(n, self.pairs_per_chunk(H, W))
-        bufs = [torch.empty(2 * per * H * W * 64, device=self.device, dtype=_tdt(self.dtype)) for _ in range(2)]
+        bufs = [torch.empty(2 * per * H * W * 64, device=self.device, dtype=_lib.torch_dtype(self.dtype)) for _ in range(2)]
         scratch = torch.empty(max(1, head_scratch_bytes(per, H * W) // 8), device=self.device, dtype=torch.float64)
         for s in range(0, n, per):
             self._chunk(x, y, pairs[s:s + per], out[s:s + per], None if lay is None else lay[s:s + per], bufs, scratch, tap)
@@ -363,7 +355,7 @@ class LPIPS:
     def _dgrad_weights(self):
         """the 13 data-gradient weights, prepared at the first backward"""
         if self.__dict__.get("_wd") is None:
-            tdt = _tdt(self.dtype)
+            tdt = _lib.torch_dtype(self.dtype)
             self._wd = [arrange_weight_dgrad(self._w_raw[k].to(self.device), tdt) for k in range(len(self.convs))]
         return self._wd
 
@@ -384,7 +376,7 @@ class LPIPS:
     def _chunk_grad(self, x, y, frames, frames_host, out, seed, coef_p, factor, scratch, flags, keep):
         m = int(frames.shape[0])
         H, W = int(x.shape[3]), int(x.shape[4])
-        tdt, dev = _tdt(self.dtype), self.device
+        tdt, dev = _lib.torch_dtype(self.dtype), self.device
         # forward, every convolution output kept
         cur = torch.empty(2 * m, H, W, 3, device=dev, dtype=tdt)
         lpips_input(x, frames, cur[:m], self.shift, self.scale, self.dtype)

@@ -49,10 +49,6 @@ def _need(who, t, dtype, ndim=None):
     return t.contiguous()
 
 
-def _scratch(nbytes, device):
-    return torch.empty(max(1, _cdiv(nbytes, 8)), device=device, dtype=torch.float64)
-
-
 # ---- device side -----------------------------------------------------------------------------------------------------------------
 def abs_diff_sum(x, y):
     """x, y float32 [B, ...] on the GPU -> float64 [B]: sum |x - y| per clip"""
@@ -63,7 +59,7 @@ def abs_diff_sum(x, y):
     n = x.numel() // B
     out = torch.empty(B, device=x.device, dtype=torch.float64)
     nbytes = 8 * B * _cdiv(n, ABS_CHUNK)
-    scratch = _scratch(nbytes, x.device)
+    scratch = _lib.scratch(nbytes, x.device)
     _lib.check(_lib.load().mebt_op_abs_diff_sum(_lib.ptr(x), _lib.ptr(y), _lib.ptr(out), B, n, _lib.ptr(scratch), nbytes, _lib.cur_stream()))
     return out
 
@@ -79,7 +75,7 @@ def clip_quality_u8(a, b):
     sq = torch.empty(N, device=a.device, dtype=torch.int64)
     ssim = torch.empty(N, device=a.device, dtype=torch.float64)
     nbytes = 16 * N * _cdiv(max(H - 10, 1), TILE_H) * _cdiv(max(W - 10, 1), TILE_W)
-    scratch = _scratch(nbytes, a.device)
+    scratch = _lib.scratch(nbytes, a.device)
     _lib.check(_lib.load().mebt_op_clip_quality_u8(_lib.ptr(a), _lib.ptr(b), _lib.ptr(sq), _lib.ptr(ssim), N, H, W, _lib.ptr(scratch), nbytes,
                                                    _lib.cur_stream()))
     return sq.view(lead), ssim.view(lead)
@@ -103,7 +99,7 @@ def code_stats(ids, z, embeddings, hist=None):
         raise ValueError(f"code_stats: `hist` must be contiguous int64 [{n_codes}] on {ids.device}")
     sq = torch.empty(1, device=ids.device, dtype=torch.float64)
     nbytes = 8 * _cdiv(M, CODE_ROWS)
-    scratch = _scratch(nbytes, ids.device)
+    scratch = _lib.scratch(nbytes, ids.device)
     _lib.check(_lib.load().mebt_op_code_stats(_lib.ptr(ids), _lib.ptr(z), _lib.ptr(emb), _lib.ptr(hist), _lib.ptr(sq), M, n_codes, d,
                                               _lib.ptr(scratch), nbytes, _lib.cur_stream()))
     return hist, sq

@@ -196,7 +196,7 @@ class Codebook(nn.Module):
         n_total = torch.empty(n_codes, device=z.device, dtype=torch.float32)
         encode_sum = torch.empty(n_codes, d, device=z.device, dtype=torch.float32)
         nbytes = int(lib.mebt_codebook_sums_scratch_bytes(M, n_codes))
-        scratch = _scratch(nbytes, z.device)
+        scratch = _lib.scratch(nbytes, z.device)
         check(lib.mebt_op_codebook_sums(ptr(ids), ptr(z), ptr(n_total), ptr(encode_sum), M, n_codes, d, ptr(scratch), nbytes, cur_stream()))
         return n_total, encode_sum
 
@@ -216,7 +216,7 @@ class Codebook(nn.Module):
         k_rand = None if self.no_random_restart else self.restart_rows(z, restart_src, restart_noise, generator)
         restarted = torch.empty(1, device=z.device, dtype=torch.int32)
         nbytes = int(lib.mebt_codebook_ema_scratch_bytes(self.n_codes))
-        scratch = _scratch(nbytes, z.device)
+        scratch = _lib.scratch(nbytes, z.device)
         check(lib.mebt_op_codebook_ema(ptr(self.N), ptr(self.z_avg), ptr(self.embeddings), ptr(n_total), ptr(encode_sum), ptr(k_rand),
                                        ptr(restarted), self.n_codes, self.embedding_dim, float(self.restart_thres), ptr(scratch), nbytes,
                                        cur_stream()))
@@ -377,11 +377,6 @@ class _Desc(C.Structure):
         return d
 
 
-def _scratch(nbytes, device):
-    """at least `nbytes` (and one element) of 8-byte aligned device scratch for an operator that reports its need in bytes"""
-    return torch.empty(max(1, -(-nbytes // 8)), device=device, dtype=torch.float64)
-
-
 class VQGAN(nn.Module):
     def __init__(self, args):
         super().__init__()
@@ -488,10 +483,10 @@ class VQGAN(nn.Module):
 
     # ---- launch helpers ----------------------------------------------------------------------------------------------------
     def _tdt(self):
-        return torch.float16 if self.compute_dtype == "f16" else torch.float32
+        return _lib.torch_dtype(self.compute_dtype)
 
     def _code(self):
-        return _lib.F16 if self.compute_dtype == "f16" else _lib.F32
+        return _lib.dtype_code(self.compute_dtype)
 
     def _conv(self, name, x, B, dims, resid=None, in_mode=0, out_mode=0):
         """x: channels-last [B, *dims, Cin] (or the fp32 video when in_mode = 1) -> (out, out_dims)"""
@@ -618,7 +613,7 @@ class VQGAN(nn.Module):
             tiles = len(taps) * (-(-cv.cout // 64)) * (-(-cv.cin // 64))
             nsplit = max(1, min(256, -(-1024 // tiles), -(-B * int(np.prod(cls)) // 32)))
             nbytes = int(lib.mebt_conv3d_wgrad_scratch_bytes(C.byref(d), nsplit))
-            scratch = _scratch(nbytes, x.device)
+            scratch = _lib.scratch(nbytes, x.device)
             dw = torch.empty(cv.cout, len(taps), cv.cin, device=x.device, dtype=torch.float32)
             dbc = torch.empty(cv.cout, device=x.device, dtype=torch.float32)
             check(lib.mebt_op_conv3d_wgrad(self._code(), C.byref(d), ptr(dw), ptr(dbc), inv_scale, nsplit, ptr(scratch), nbytes, cur_stream()))
@@ -664,7 +659,7 @@ class VQGAN(nn.Module):
         dx = torch.empty_like(x)
         dg, dbt = torch.empty(Cc, device=x.device, dtype=torch.float32), torch.empty(Cc, device=x.device, dtype=torch.float32)
         nbytes = int(lib.mebt_groupnorm_silu_bwd_scratch_bytes(B, vox, Cc))
-        scratch = _scratch(nbytes, x.device)
+        scratch = _lib.scratch(nbytes, x.device)
         check(lib.mebt_op_groupnorm_silu_bwd(self._code(), ptr(x), ptr(stats), ptr(g), ptr(b), ptr(dy), ptr(add), ptr(dx), ptr(dg), ptr(dbt),
                                              inv_scale, B, vox, Cc, ptr(scratch), nbytes, cur_stream()))
         self._acc(gn.weight, dg, flags)

@@ -36,7 +36,8 @@ def record(name, value, gate):
 
 
 # ---- abs_diff_sum -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,n", [(1, 1), (3, 3 * 4 * 16 * 16), (2, 3 * 5 * 24 * 40 + 0), (5, 100003)])
+# the last case: 258 workgroups per clip, so the finishing kernel's threads 0 and 1 add a second slot (more than 256 slots, no multiple of it)
+@pytest.mark.parametrize("B,n", [(1, 1), (3, 3 * 4 * 16 * 16), (2, 3 * 5 * 24 * 40 + 0), (5, 100003), (1, 257 * recon.ABS_CHUNK + 5)])
 def test_abs_diff_sum_vs_twin(B, n):
     g = torch.Generator().manual_seed(n)
     x, y = torch.rand(B, n, generator=g) - 0.5, torch.rand(B, n, generator=g) - 0.5
@@ -107,7 +108,8 @@ def test_clip_quality_u8_takes_clips():
 
 
 # ---- code_stats -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("M,n_codes,d,skewed", [(64, 512, 64, False), (1000, 16384, 256, True)])
+# the last case: 258 workgroups, more slots than the finishing kernel has threads and no multiple of them
+@pytest.mark.parametrize("M,n_codes,d,skewed", [(64, 512, 64, False), (1000, 16384, 256, True), (257 * recon.CODE_ROWS + 1, 1, 1, False)])
 def test_code_stats_vs_twin(M, n_codes, d, skewed):
     g = torch.Generator().manual_seed(M)
     z, e = torch.randn(M, d, generator=g), torch.randn(n_codes, d, generator=g)
