@@ -631,6 +631,28 @@ int mebt_op_conv2d_3x3_dgrad(int32_t dtype, const void* dy, const void* w_dgrad,
 int mebt_op_lpips_input_bwd(int32_t dtype, const void* d_in, const int32_t* frames, const int32_t* frames_host, float* seed, int32_t B,
                             int32_t T, int32_t H, int32_t W, int64_t n_frames, const float* scale, float factor, mebt_stream_t stream);
 
+/* ---- First-stage discriminators: BatchNorm statistics and loss values (csrc/disc/disc.hip; reference mebt/vqgan.py:27-37,416-520;
+ * DESIGN.md §9i) ---------------------------------------------------------------------------------------------------------------------
+ * Maps are channels-last [M, C] of `dtype` (MEBT_DTYPE_F16 or MEBT_DTYPE_F32); sums are fp64, offsets 64-bit, every entry checks its
+ * arguments before it launches and allocates nothing.  No float atomics: the same input gives the same bits on every run. */
+#define MEBT_DISC_BN_ROWS 128           /* rows per workgroup (= per slot) of the BatchNorm partials */
+/* Per channel c and slot g the fp64 {sum, sum of squares} of rows [g R, (g + 1) R) of x [M, C], R = MEBT_DISC_BN_ROWS, at
+ * slots[(c * 2 + q) * n_slots + g], n_slots = ceil(M / R); slots: 8-byte aligned, slots_bytes >= 16 * C * n_slots. */
+int mebt_op_disc_bn_partials(int32_t dtype, const void* x, int64_t M, int32_t C, void* slots, int64_t slots_bytes, mebt_stream_t stream);
+/* Adds each channel's n_slots slots in index order (fp64) -> stats fp32 [2][C] = mean, 1 / sqrt(max(var, 0) + 1e-5) with the biased
+ * variance over `count` values per channel.  update != 0: running_mean / running_var (fp32 [C]) move by momentum 0.1 towards the mean
+ * and the unbiased variance, *num_batches_tracked (int64 on the device, may be NULL) += 1: nn.BatchNorm's training-mode bookkeeping.
+ * count < 2: MEBT_STATUS_ESHAPE ("expected more than 1 value per channel when training"). */
+int mebt_op_disc_bn_finish(const void* slots, int64_t n_slots, int32_t C, int64_t count, float* stats, float* running_mean, float* running_var,
+                           int64_t* num_batches_tracked, int32_t update, mebt_stream_t stream);
+/* fp64 means in fixed order.  n_logits > 0: out[0..4] = mean of l, relu(1 - l), relu(1 + l), softplus(-l), softplus(l) over logits
+ * [n_logits] of `dtype` (the halves of hinge_d_loss / vanilla_d_loss and the generator term).  n_feat > 0: out[5] = mean |a - b| of two
+ * feature tensors [n_feat] of `dtype` (feature matching).  Entries not asked for are left alone.  scratch: 8-byte aligned,
+ * mebt_disc_losses_scratch_bytes(n_logits, n_feat) bytes. */
+int64_t mebt_disc_losses_scratch_bytes(int64_t n_logits, int64_t n_feat);
+int mebt_op_disc_losses(int32_t dtype, const void* logits, int64_t n_logits, const void* feat_a, const void* feat_b, int64_t n_feat, double* out,
+                        void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
+
 /* ---- instrumentation ----------------------------------------------------------------------------- */
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py roofline): enable, run,
  * then read {launches, total ms, total algorithmic flops} of the GEMM family (family 0), or the

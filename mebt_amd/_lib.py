@@ -142,6 +142,10 @@ PROTOTYPES = {
     "mebt_op_maxpool_2x2_bwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mebt_op_conv2d_3x3_dgrad": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 5 + [c_vp]),
     "mebt_op_lpips_input_bwd": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, C.POINTER(c_f32), c_f32, c_vp]),
+    "mebt_op_disc_bn_partials": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "mebt_op_disc_bn_finish": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mebt_disc_losses_scratch_bytes": (c_i64, [c_i64, c_i64]),
+    "mebt_op_disc_losses": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "mebt_debug_dropout_mask": (c_i32, [C.c_uint64, C.c_uint32, c_f32, c_i64, c_vp, c_vp]),
     "mebt_debug_clock_probe": (c_i32, [c_vp, C.c_uint64, c_vp]),
     "mebt_debug_side_stream": (None, [c_vp, c_i32]),
