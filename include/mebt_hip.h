@@ -653,6 +653,33 @@ int64_t mebt_disc_losses_scratch_bytes(int64_t n_logits, int64_t n_feat);
 int mebt_op_disc_losses(int32_t dtype, const void* logits, int64_t n_logits, const void* feat_a, const void* feat_b, int64_t n_feat, double* out,
                         void* scratch, int64_t scratch_bytes, mebt_stream_t stream);
 
+/* ---- First-stage discriminators: the forward (csrc/disc/disc_conv.hip, addressing in csrc/disc/disc_addr.h; reference
+ * mebt/vqgan.py:416-520) ----------------------------------------------------------------------------------------------
+ * Maps are channels-last [B, T, H, W, C] of `dtype` (T = 1 for the image network), 16-byte aligned.  A stage is the 4^d convolution
+ * (kt 1 with Ti = 1, or kt 4), stride 1 or 2, zero padding 2 per side: To / Ho / Wo must equal n / 2 + 1 at stride 2 and n + 1 at
+ * stride 1.  Cin is the channel count as stored: 4, or a multiple of the 16-byte vector (8 fp16, 4 fp32).  Weights are pre-arranged
+ * [Npad][Kpad] of `dtype` (Npad = Cout rounded up to 64, Kpad = kt * 16 * Cin rounded up to 32, K order (tap, ci) with ci fastest, zeros
+ * in the padding): w_bytes must be exactly that.  bias: fp32 [Cout].  Every entry checks its arguments in a fixed order before it
+ * launches and allocates nothing; an output row's accumulation order does not depend on M, the batch or its tile. */
+/* x fp32 [B, 3, T, H, W] -> out [B, To, H, W, 4] of `dtype`, fourth channel 0.  frame_idx NULL: To = T; else int64 [B] on the device,
+ * each in [0, T) (the caller checks), To = 1: frame frame_idx[b] of clip b (vqgan.py:104-108). */
+int mebt_op_disc_ingest(int32_t dtype, const float* x, const int64_t* frame_idx, void* out, int64_t out_bytes, int32_t B, int32_t T, int32_t H,
+                        int32_t W, mebt_stream_t stream);
+/* out [B, To, Ho, Wo, Cout] = conv(in) + bias, with LeakyReLU(0.2) when act != 0.  slots != NULL: also the BatchNorm partials of the
+ * fp32 value (before the activation and before it is rounded to `dtype`), fp64 {sum, sum of squares} per channel and row tile in the
+ * layout mebt_op_disc_bn_finish reads with n_slots = ceil(M / BM), BM = 128 (fp16) or 64 (fp32), M = B To Ho Wo; slots_bytes >=
+ * 16 * Cout * n_slots. */
+int mebt_op_disc_conv(int32_t dtype, const void* in, int64_t in_bytes, const void* w, int64_t w_bytes, const float* bias, void* out,
+                      int64_t out_bytes, void* slots, int64_t slots_bytes, int32_t B, int32_t Ti, int32_t Hi, int32_t Wi, int32_t Cin, int32_t kt,
+                      int32_t stride, int32_t To, int32_t Ho, int32_t Wo, int32_t Cout, int32_t act, mebt_stream_t stream);
+/* In place on x [M, C] (C a multiple of 4): (x - mean) * rstd * gamma + beta, then LeakyReLU(0.2); stats fp32 [2][C] = mean, rstd as
+ * mebt_op_disc_bn_finish writes them; gamma, beta fp32 [C]. */
+int mebt_op_disc_bn_act(int32_t dtype, void* x, int64_t M, int32_t C, const float* stats, const float* gamma, const float* beta, mebt_stream_t stream);
+/* The last stage (Cout 1, stride 1, no activation): out [B, To, Ho, Wo, 1]; w is the arranged [64][Kpad], of which row 0 is read. */
+int mebt_op_disc_head(int32_t dtype, const void* in, int64_t in_bytes, const void* w, int64_t w_bytes, const float* bias, void* out,
+                      int64_t out_bytes, int32_t B, int32_t Ti, int32_t Hi, int32_t Wi, int32_t Cin, int32_t kt, int32_t To, int32_t Ho, int32_t Wo,
+                      mebt_stream_t stream);
+
 /* ---- instrumentation ----------------------------------------------------------------------------- */
 /* Per-kernel-family timing with HIP events on the launch stream (bench.py roofline): enable, run,
  * then read {launches, total ms, total algorithmic flops} of the GEMM family (family 0), or the

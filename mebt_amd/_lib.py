@@ -146,6 +146,10 @@ PROTOTYPES = {
     "mebt_op_disc_bn_finish": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mebt_disc_losses_scratch_bytes": (c_i64, [c_i64, c_i64]),
     "mebt_op_disc_losses": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "mebt_op_disc_ingest": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64] + [c_i32] * 4 + [c_vp]),
+    "mebt_op_disc_conv": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64] + [c_i32] * 12 + [c_vp]),
+    "mebt_op_disc_bn_act": (c_i32, [c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "mebt_op_disc_head": (c_i32, [c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64] + [c_i32] * 9 + [c_vp]),
     "mebt_debug_dropout_mask": (c_i32, [C.c_uint64, C.c_uint32, c_f32, c_i64, c_vp, c_vp]),
     "mebt_debug_clock_probe": (c_i32, [c_vp, C.c_uint64, c_vp]),
     "mebt_debug_side_stream": (None, [c_vp, c_i32]),

@@ -1,5 +1,5 @@
 // First-stage discriminators (reference mebt/vqgan.py:27-37,416-520), the reductions: BatchNorm batch statistics and the values of the
-// GAN losses.  DESIGN.md §9i.  The convolutions and the normalisation pass are not in this file yet.
+// GAN losses.  DESIGN.md §9i.  The convolutions and the normalisation pass are in disc_conv.hip.
 //
 // Layout: a map is channels-last [M, C] (M = batch x voxels) of `dtype`: fp16 or fp32.  Sums are fp64 from the element on and every
 // offset is 64-bit.  No float atomics and no reduction whose order depends on the launch: a workgroup adds its rows (or elements) in

@@ -5,8 +5,10 @@
 - the two networks as nn.Modules that HOLD parameters and buffers under the reference's keys (`model{n}.0.weight`,
   `model{n}.1.running_var`, ...), so a state dict loads with strict=True in both directions (the reference's `nn.SyncBatchNorm` and the
   `nn.BatchNorm{2,3}d` holders here carry the same five entries), with their launch geometry (`layer_plan`) and torch's refusal of a
-  training-mode BatchNorm over one value per channel.  Their `forward` is NOT built: the convolution and normalisation kernels are
-  separate work, and calling it raises;
+  training-mode BatchNorm over one value per channel.  A holder's own `forward` raises: the compute lives in `DiscRunner`;
+- the forward on the HIP kernels of csrc/disc/disc_conv.hip (`arrange_weight`, `ingest`, `conv_stage`, `bn_act`, `head_stage`,
+  `DiscRunner`): ingest to channels-last, the 4^d strided convolutions with their BatchNorm partials, the normalise + LeakyReLU pass
+  and the one-channel last stage; and `gan_terms`, the reference's thirteen logged GAN values from the two runners;
 - reading the two networks out of a first-stage checkpoint (`extract`, `read_file`, `load_discriminators`); `VQGAN.load_state_dict`
   keeps skipping these keys;
 - on the HIP reductions of csrc/disc/disc.hip: BatchNorm batch statistics with the running-buffer update (`batch_stats`) and the loss
@@ -184,8 +186,8 @@ class _PatchDiscriminator(nn.Module):
         return plan
 
     def forward(self, input, update_running=True):
-        raise NotImplementedError(f"{type(self).__name__}.forward is not built: this module holds the reference's parameters and buffers; the "
-                                  "convolution and normalisation kernels of the discriminators are separate work (DESIGN.md §9i)")
+        raise NotImplementedError(f"{type(self).__name__}.forward is not built: this module holds the reference's parameters and buffers; "
+                                  "DiscRunner(net) runs the forward on the HIP kernels (DESIGN.md §9i)")
 
 
 class NLayerDiscriminator(_PatchDiscriminator):
@@ -227,6 +229,312 @@ def _hp(args, name, default=None):
     if isinstance(args, dict):
         return args.get(name, default)
     return getattr(args, name, default)
+
+
+# ---- the forward (device) ------------------------------------------------------------------------------------------------------------------
+TILE_ROWS = {"f16": 128, "f32": 64}    # TileCfg<T>::BM of csrc/mfma_tile.h: rows per BatchNorm slot of the convolution's epilogue
+
+
+def _dtype_name(dtype):
+    if dtype in ("f16", "f32"):
+        return dtype
+    if dtype in (torch.float16, torch.float32):
+        return "f16" if dtype == torch.float16 else "f32"
+    raise ValueError(f"dtype must be 'f16' or 'f32', not {dtype!r}")
+
+
+def arrange_weight(w, dtype, cin_store=None):
+    """[Cout, Cin, (4,) 4, 4] -> [Npad, Kpad] of `dtype` in the kernels' K order: k = tap * cin_store + ci, tap = (dt * 4 + dh) * 4 + dw;
+    cin_store (default Cin rounded up to 4) is the channel count as stored, the extra channels' columns are zero, as are the rows
+    from Cout to Npad (a multiple of 64) and the columns from K to Kpad (a multiple of 32).  Host torch, any device."""
+    tdt = _lib.torch_dtype(_dtype_name(dtype))
+    if not torch.is_tensor(w) or w.dim() not in (4, 5) or any(k != 4 for k in w.shape[2:]):
+        raise ValueError(f"arrange_weight expects [Cout, Cin, (4,) 4, 4], got {tuple(w.shape) if torch.is_tensor(w) else type(w).__name__}")
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    cs = -(-cin // 4) * 4 if cin_store is None else int(cin_store)
+    if cs < cin or cs % 4:
+        raise ValueError(f"cin_store must be a multiple of 4 and at least Cin = {cin}, got {cin_store}")
+    taps = w[0, 0].numel()
+    K = taps * cs
+    body = torch.zeros(cout, taps, cs, dtype=tdt, device=w.device)
+    body[:, :, :cin] = w.detach().reshape(cout, cin, taps).permute(0, 2, 1).to(tdt)
+    out = torch.zeros(-(-cout // 64) * 64, -(-K // 32) * 32, dtype=tdt, device=w.device)
+    out[:cout, :K] = body.reshape(cout, K)
+    return out
+
+
+def _check_map(name, x, dt=None):
+    """a channels-last map [B, T, H, W, C] a kernel reads through its raw pointer"""
+    if not torch.is_tensor(x) or x.dim() != 5 or not x.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous channels-last [B, T, H, W, C] tensor")
+    code = _code_of(x)
+    if dt is not None and code != dt:
+        raise ValueError(f"{name} must be {dt}, got {x.dtype}")
+    return code
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def ingest(x, dtype, frame_idx=None):
+    """fp32 [B, 3, T, H, W] (or [B, 3, H, W]) on the GPU -> channels-last [B, To, H, W, 4] of `dtype`, fourth channel 0.  frame_idx
+    (int64 [B] on x's device, each in [0, T): the caller has checked) picks that frame of every clip, To = 1 (vqgan.py:104-108)."""
+    dt = _dtype_name(dtype)
+    if not torch.is_tensor(x) or x.dim() not in (4, 5) or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise ValueError(f"ingest expects fp32 [B, 3, (T,) H, W], got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    _check_on_gpu("x", x)
+    x = x.contiguous()
+    B, T, H, W = (x.shape[0], 1, x.shape[2], x.shape[3]) if x.dim() == 4 else (x.shape[0], x.shape[2], x.shape[3], x.shape[4])
+    if frame_idx is not None:
+        _check_buffer("frame_idx", frame_idx, torch.int64, B)
+        if frame_idx.device != x.device:
+            raise RuntimeError(f"frame_idx must live on x's device {x.device}")
+    out = torch.empty(B, 1 if frame_idx is not None else T, H, W, 4, device=x.device, dtype=_lib.torch_dtype(dt))
+    check(_lib.load().mebt_op_disc_ingest(_lib.dtype_code(dt), ptr(x), ptr(frame_idx), ptr(out), _nbytes(out), B, T, H, W, cur_stream()))
+    return out
+
+
+def _stage_dims(x, kt, stride):
+    B, Ti, Hi, Wi, Cin = x.shape
+    ext = (lambda n: n // 2 + 1) if stride == 2 else (lambda n: n + 1)
+    return B, Ti, Hi, Wi, Cin, (ext(Ti) if kt == 4 else 1), ext(Hi), ext(Wi)
+
+
+def conv_stage(x, w, bias, kt, stride, cout, act=False, slots=False):
+    """One 4^d convolution (kt 1: 4 x 4 on maps with T = 1; kt 4: 4 x 4 x 4), zero padding 2, on a channels-last map x [B, T, H, W, Cin]
+    with `w` from arrange_weight and fp32 bias [cout]: the map [B, To, Ho, Wo, cout] in x's dtype, with LeakyReLU(0.2) when `act`.
+    slots=True: also the fp64 BatchNorm partials [cout * 2 * n_slots] of the unrounded values, for mebt_op_disc_bn_finish."""
+    dt = _check_map("x", x)
+    if w.dtype != x.dtype or w.device != x.device or not w.is_contiguous() or bias.dtype != torch.float32 or bias.device != x.device \
+            or bias.numel() != cout or not bias.is_contiguous():
+        raise ValueError("conv_stage: w must be arrange_weight's tensor in x's dtype and bias fp32 [cout], both on x's device")
+    B, Ti, Hi, Wi, Cin, To, Ho, Wo = _stage_dims(x, kt, stride)
+    out = torch.empty(B, To, Ho, Wo, cout, device=x.device, dtype=x.dtype)
+    sl = None
+    if slots:
+        sl = torch.empty(cout * 2 * -(-(B * To * Ho * Wo) // TILE_ROWS[dt]), device=x.device, dtype=torch.float64)
+    check(_lib.load().mebt_op_disc_conv(_lib.dtype_code(dt), ptr(x), _nbytes(x), ptr(w), _nbytes(w), ptr(bias), ptr(out), _nbytes(out), ptr(sl),
+                                        0 if sl is None else sl.numel() * 8, B, Ti, Hi, Wi, Cin, kt, stride, To, Ho, Wo, cout, int(bool(act)),
+                                        cur_stream()))
+    return (out, sl) if slots else out
+
+
+def head_stage(x, w, bias, kt):
+    """The last stage (one output channel, stride 1, no activation): [B, To, Ho, Wo, 1] in x's dtype"""
+    dt = _check_map("x", x)
+    if w.dtype != x.dtype or w.device != x.device or not w.is_contiguous() or bias.dtype != torch.float32 or bias.device != x.device \
+            or bias.numel() != 1:
+        raise ValueError("head_stage: w must be arrange_weight's tensor in x's dtype and bias fp32 [1], both on x's device")
+    B, Ti, Hi, Wi, Cin, To, Ho, Wo = _stage_dims(x, kt, 1)
+    out = torch.empty(B, To, Ho, Wo, 1, device=x.device, dtype=x.dtype)
+    check(_lib.load().mebt_op_disc_head(_lib.dtype_code(dt), ptr(x), _nbytes(x), ptr(w), _nbytes(w), ptr(bias), ptr(out), _nbytes(out), B, Ti, Hi,
+                                        Wi, Cin, kt, To, Ho, Wo, cur_stream()))
+    return out
+
+
+def slot_stats(slots, count, cout, running_mean=None, running_var=None, num_batches=None, update=False):
+    """the convolution's slots -> stats fp32 [2, cout] = (mean, rstd) through mebt_op_disc_bn_finish, which also moves the running
+    buffers (fp32 [cout], int64 [1] on the slots' device, contiguous) when `update`"""
+    if count <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got {count} value(s)")
+    for name, t, want, numel in (("running_mean", running_mean, torch.float32, cout), ("running_var", running_var, torch.float32, cout),
+                                 ("num_batches", num_batches, torch.int64, 1)):
+        if t is not None:
+            _check_buffer(name, t, want, numel)
+            if t.device != slots.device:
+                raise RuntimeError(f"{name} must live on the GPU with the map, got {t.device}")
+    if update and (running_mean is None or running_var is None):
+        raise ValueError("update=True needs running_mean and running_var")
+    stats = torch.empty(2, cout, device=slots.device, dtype=torch.float32)
+    check(_lib.load().mebt_op_disc_bn_finish(ptr(slots), slots.numel() // (2 * cout), cout, count, ptr(stats), ptr(running_mean), ptr(running_var),
+                                             ptr(num_batches), int(bool(update)), cur_stream()))
+    return stats
+
+
+def bn_act(x, stats, gamma, beta):
+    """in place on a channels-last map: (x - mean) * rstd * gamma + beta, then LeakyReLU(0.2); stats fp32 [2, C], gamma / beta fp32 [C]"""
+    _check_map("x", x)
+    Cc = x.shape[-1]
+    for name, t, numel in (("stats", stats, 2 * Cc), ("gamma", gamma, Cc), ("beta", beta, Cc)):
+        _check_buffer(name, t, torch.float32, numel)
+        if t.device != x.device:
+            raise RuntimeError(f"{name} must live on the GPU with the map, got {t.device}")
+    check(_lib.load().mebt_op_disc_bn_act(_lib.dtype_code(_code_of(x)), ptr(x), x.numel() // Cc, Cc, ptr(stats), ptr(gamma), ptr(beta), cur_stream()))
+    return x
+
+
+def _frame_index(frame_idx, B, T, device):
+    """frame_idx (a sequence or an integer tensor [B]) checked against [0, T) on the host, as int64 on `device`.  A tensor that already
+    lives on a GPU is read back for the check (one synchronisation); hand over a host tensor to avoid it."""
+    fi = torch.as_tensor(frame_idx)
+    if fi.dtype.is_floating_point or fi.dtype == torch.bool or fi.dim() != 1 or fi.numel() != B:
+        raise ValueError(f"frame_idx must hold {B} integer(s), one per clip, got {tuple(fi.shape)} of {fi.dtype}")
+    host = fi.detach().to("cpu", torch.int64)
+    if int(host.min()) < 0 or int(host.max()) >= T:
+        raise ValueError(f"frame_idx must lie in [0, {T}), got {host.tolist()[:8]}")
+    return fi.to(device, torch.int64).contiguous() if fi.device.type == "cuda" else host.to(device)
+
+
+class _CheckedFrames:
+    """a frame index that `_frame_index` has checked and moved to the device (gan_terms checks once for its four calls)"""
+    def __init__(self, dev_idx):
+        self.dev_idx = dev_idx
+
+
+class DiscRunner:
+    """The forward of one PatchGAN holder on the HIP kernels.  Holds the arranged weights, biases and BatchNorm affine tensors on the
+    holder's device in the compute dtype (`dtype`, default the holder's `compute_dtype`); `refresh()` re-derives them and runs by
+    itself whenever a parameter's `_version` has moved (an optimizer step, a `load_state_dict`).  The running buffers are read from,
+    and in training mode written to, the holder itself."""
+
+    def __init__(self, net, dtype=None):
+        if not isinstance(net, _PatchDiscriminator):
+            raise TypeError(f"DiscRunner expects an NLayerDiscriminator or NLayerDiscriminator3D, got {type(net).__name__}")
+        self.net = net
+        self.dtype = _dtype_name(dtype if dtype is not None else net.compute_dtype)
+        self.kt = 4 if net.three_d else 1
+        self.refresh()
+
+    def _params(self):
+        return list(self.net.parameters())
+
+    def refresh(self):
+        net = self.net
+        self.stages = []
+        with torch.no_grad():
+            for n, (cin, cout, stride, bn, act) in enumerate(stage_channels(net.input_nc, net.ndf, net.n_layers)):
+                seq = getattr(net, f"model{n}")
+                e = dict(cout=cout, stride=stride, bn=bn, act=act, w=arrange_weight(seq[0].weight, self.dtype, 4 if n == 0 else None),
+                         bias=seq[0].bias.detach().to(torch.float32).clone().contiguous())
+                if bn:
+                    e["gamma"] = seq[1].weight.detach().to(torch.float32).clone().contiguous()
+                    e["beta"] = seq[1].bias.detach().to(torch.float32).clone().contiguous()
+                    e["norm"] = seq[1]
+                self.stages.append(e)
+        self._seen = [(p, p._version, p.device) for p in self._params()]
+
+    def _stale(self):
+        now = self._params()
+        return len(now) != len(self._seen) or any(p is not q or p._version != v or p.device != d for p, (q, v, d) in zip(now, self._seen))
+
+    def _eval_stats(self, st):
+        """fp32 [2, C] = (running_mean, 1 / sqrt(running_var + eps)), computed in fp64; kept until a buffer's `_version` moves"""
+        norm = st["norm"]
+        rm, rv = norm.running_mean, norm.running_var
+        held = st.get("eval_stats")
+        if held is None or held[0] is not rm or held[1] is not rv or held[2] != (rm._version, rv._version, rm.device):
+            with torch.no_grad():
+                stats = torch.stack([rm.double(), 1.0 / torch.sqrt(rv.double() + BN_EPS)]).to(torch.float32).contiguous()
+            st["eval_stats"] = held = (rm, rv, (rm._version, rv._version, rm.device), stats)
+        return held[3]
+
+    def _logical_shape(self, x, frame_idx):
+        if not torch.is_tensor(x):
+            raise ValueError(f"DiscRunner expects a tensor, got {type(x).__name__}")
+        if frame_idx is None:
+            return tuple(x.shape)
+        if self.net.three_d or x.dim() != 5:
+            raise ValueError("frame_idx picks one frame per clip for the image network: it needs NLayerDiscriminator and x [B, 3, T, H, W], "
+                             f"got {type(self.net).__name__} and {tuple(x.shape)}")
+        return tuple(x.shape[:2]) + tuple(x.shape[3:])
+
+    def forward_buffers(self, x, frame_idx=None, update_running=None):
+        """the stage outputs as the channels-last buffers [B, T, H, W, C] the kernels wrote (the last one is the logits)"""
+        net = self.net
+        plan = net.check_batch(self._logical_shape(x, frame_idx))          # every shape refusal and torch's ValueError: before any launch
+        if x.dtype != torch.float32:
+            raise ValueError(f"DiscRunner takes the fp32 input of the reference, got {x.dtype}")
+        fidx = None
+        if isinstance(frame_idx, _CheckedFrames):
+            fidx = frame_idx.dev_idx
+        elif frame_idx is not None:
+            fidx = _frame_index(frame_idx, x.shape[0], x.shape[2], x.device)
+        _check_on_gpu("x", x)
+        held = self._params()[0]
+        _check_on_gpu(f"{type(net).__name__} (DiscRunner's holder)", held)
+        if held.device != x.device:
+            raise RuntimeError(f"x must live on the holder's device {held.device}, got {x.device}")
+        if self._stale():
+            self.refresh()
+        training = net.training
+        update = training and update_running is not False
+        h = ingest(x, self.dtype, fidx)
+        bufs = []
+        for e, st in zip(plan, self.stages):
+            if st["cout"] == 1 and not st["act"]:
+                h = head_stage(h, st["w"], st["bias"], self.kt)
+            elif not st["bn"]:
+                h = conv_stage(h, st["w"], st["bias"], self.kt, st["stride"], st["cout"], act=st["act"])
+            else:
+                norm = st["norm"]
+                if training:
+                    h, slots = conv_stage(h, st["w"], st["bias"], self.kt, st["stride"], st["cout"], slots=True)
+                    nbt = norm.num_batches_tracked
+                    stats = slot_stats(slots, h.numel() // st["cout"], st["cout"], norm.running_mean, norm.running_var,
+                                       nbt.view(1) if update else None, update)
+                    if update:                          # the kernel wrote them through raw pointers: say so, as an in-place op would
+                        for t in (norm.running_mean, norm.running_var, nbt):
+                            torch.autograd.graph.increment_version(t)
+                else:
+                    h = conv_stage(h, st["w"], st["bias"], self.kt, st["stride"], st["cout"])
+                    stats = self._eval_stats(st)
+                bn_act(h, stats, st["gamma"], st["beta"])
+            bufs.append(h)
+        return bufs
+
+    def __call__(self, x, frame_idx=None, update_running=None):
+        """x fp32 [B, 3, T, H, W] (video network), [B, 3, H, W] (image network), or [B, 3, T, H, W] with frame_idx (image network: frame
+        frame_idx[b] of clip b) -> (logits, [stage outputs]) in the reference's logical shapes, as views of the channels-last buffers.
+        The mode follows net.training; training uses batch statistics and advances the running buffers unless update_running=False."""
+        bufs = self.forward_buffers(x, frame_idx, update_running)
+        feats = [b.permute(0, 4, 1, 2, 3) if self.net.three_d else b[:, 0].permute(0, 3, 1, 2) for b in bufs]
+        return feats[-1], feats
+
+
+def gan_terms(args, image_runner, video_runner, x, x_recon, frame_idx, global_step, which, update_running=True):
+    """The values the reference logs in its GAN phase (vqgan.py:118-141 for which="generator", :156-165 for "discriminator"), from the
+    two runners and the HIP reductions: a dict of 0-dim fp64 device tensors under G_KEYS or D_KEYS; same contract as gan_terms_twin.
+    x, x_recon fp32 [B, 3, T, H, W] on the GPU; frame_idx [B] (a host sequence or tensor: checked on the host, no synchronisation).
+    Real and fake go through the networks as separate calls, each a BatchNorm batch of its own, in the reference's order; the
+    real-side feature passes run only where the matching GAN weight is > 0.  The mode follows the holders' `training`."""
+    if which not in ("generator", "discriminator"):
+        raise ValueError(f"which must be 'generator' or 'discriminator', not {which!r}")
+    for name, t in (("x", x), ("x_recon", x_recon)):
+        if not torch.is_tensor(t) or t.dim() != 5:
+            raise ValueError(f"gan_terms: {name} must be [B, 3, T, H, W], got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if x.shape != x_recon.shape:
+        raise ValueError(f"gan_terms: x and x_recon differ in shape, {tuple(x.shape)} and {tuple(x_recon.shape)}")
+    if image_runner.net.three_d or not video_runner.net.three_d:
+        raise ValueError("gan_terms expects (image runner, video runner) in this order")
+    frame_shape = tuple(x.shape[:2]) + tuple(x.shape[3:])
+    image_runner.net.check_batch(frame_shape)
+    video_runner.net.check_batch(tuple(x.shape))
+    fidx = _frame_index(frame_idx, x.shape[0], x.shape[2], x.device)
+    _check_on_gpu("x", x)
+    _check_on_gpu("x_recon", x_recon)
+    frames = _CheckedFrames(fidx)
+    iw, vw = float(_hp(args, "image_gan_weight", 1.0)), float(_hp(args, "video_gan_weight", 1.0))
+    factor = adopt_weight(global_step, threshold=int(_hp(args, "discriminator_iter_start", 50000)))
+    image = lambda v: image_runner.forward_buffers(v, frames, update_running)
+    video = lambda v: video_runner.forward_buffers(v, None, update_running)
+    if which == "generator":
+        pi, pv = image(x_recon), video(x_recon)
+        out = {"g_image_loss": -disc_losses(logits=pi[-1])[0], "g_video_loss": -disc_losses(logits=pv[-1])[0]}
+        out["aeloss"] = factor * (iw * out["g_image_loss"] + vw * out["g_video_loss"])
+        zero = torch.zeros((), device=x.device, dtype=torch.float64)
+        out["image_gan_feat_loss"] = feature_matching(pi, image(x)) if iw > 0 else zero
+        out["video_gan_feat_loss"] = feature_matching(pv, video(x)) if vw > 0 else zero
+        out["gan_feat_loss"] = factor * float(_hp(args, "gan_feat_weight", 0.0)) * (out["image_gan_feat_loss"] + out["video_gan_feat_loss"])
+        return out
+    d_loss = hinge_d_loss if _hp(args, "disc_loss_type", "hinge") == "hinge" else vanilla_d_loss
+    ir, vr = image(x)[-1], video(x)[-1]
+    if_, vf = image(x_recon)[-1], video(x_recon)[-1]
+    out = {"logits_image_real": disc_losses(logits=ir)[0], "logits_image_fake": disc_losses(logits=if_)[0],
+           "logits_video_real": disc_losses(logits=vr)[0], "logits_video_fake": disc_losses(logits=vf)[0],
+           "d_image_loss": d_loss(ir, if_), "d_video_loss": d_loss(vr, vf)}
+    out["discloss"] = factor * (iw * out["d_image_loss"] + vw * out["d_video_loss"])
+    return out
 
 
 # ---- checkpoint access ---------------------------------------------------------------------------------------------------------------------

@@ -7,7 +7,12 @@ Flags: the data flags of VideoData (as `mebt_amd.measure_fvd` takes them), `--vq
 [N, T, H, W, 3]), `--compute_fvd` with the I3D flags of measure_fvd (`--i3d_ckpt --i3d_dtype --i3d_batch`), and `--lpips` with
 `--lpips_ckpt FILE` (default: the `perceptual_model.*` tensors inside `--vqgan_ckpt`), `--lpips_dtype {f16,f32}` and `--lpips_every K`
 (every K-th frame of a clip, default 1): the VGG-16 perceptual distance between the float clips and their reconstructions
-(mebt_amd/lpips.py), the mean over all scored frames.
+(mebt_amd/lpips.py), the mean over all scored frames.  `--disc` adds the thirteen values the reference logs in its GAN phase
+(vqgan.py:118-141,156-165: g_image_loss ... discloss, `discriminator.G_KEYS + D_KEYS`), computed per batch from the checkpoint's two
+PatchGAN discriminators on the clips and their reconstructions and averaged over the batches: `--disc_dtype {f16,f32}` is the compute
+dtype, `--disc_stats {batch,running}` the BatchNorm mode (`batch`, the default: batch statistics with the buffers left untouched, as
+the reference logs these values in training mode; `running`: eval mode); one frame per clip is drawn per batch from a generator seeded
+by `--seed`, and `global_step` is the checkpoint's (0 when it has none).
 
 Real side: `--image_folder` with `--data_path` a frame folder (train.txt under `--train`, else test.txt) is read through
 `VideoData(..., raw=True)`: the workers only decode, crop / resize / normalisation run in the frame-ingest kernel; with
@@ -32,7 +37,10 @@ from .data import TokenData
 from .measure_fvd import add_scoring_args, frame_folder, write_csv
 
 
+from .discriminator import D_KEYS, G_KEYS
+
 LPIPS_DTYPE_DEFAULT = 'f16'
+DISC_COLUMNS = list(G_KEYS + D_KEYS)
 
 
 def build_parser():
@@ -49,6 +57,10 @@ def build_parser():
     parser.add_argument('--lpips_ckpt', type=str, default='', help="a state dict with the LPIPS tensors; default: those inside --vqgan_ckpt")
     parser.add_argument('--lpips_dtype', type=str, default=LPIPS_DTYPE_DEFAULT, choices=['f16', 'f32'])
     parser.add_argument('--lpips_every', type=int, default=1, help='score every K-th frame of a clip')
+    parser.add_argument('--disc', action='store_true', help="add the thirteen GAN-phase values of the checkpoint's discriminators")
+    parser.add_argument('--disc_dtype', type=str, default='f16', choices=['f16', 'f32'])
+    parser.add_argument('--disc_stats', type=str, default='batch', choices=['batch', 'running'],
+                        help='BatchNorm statistics: of the batch (buffers untouched) or the running buffers (eval mode)')
     return add_scoring_args(parser)              # --train --packed_path --compute_fvd --i3d_ckpt --i3d_dtype --i3d_batch
 
 
@@ -56,6 +68,45 @@ def seed_everything(seed):
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
+
+
+class DiscTerms:
+    """The function behind --disc: the thirteen GAN-phase values per batch from a checkpoint's discriminators (discriminator.gan_terms,
+    generator and discriminator side), kept on the device; `result()` reads the means over the batches back once."""
+
+    def __init__(self, ckpt, device, dtype='f16', stats='batch', seed=0):
+        from . import discriminator as D
+        from .lightning_shim import load_checkpoint_file
+        try:
+            nets = D.load_discriminators(ckpt, device, dtype)
+        except ValueError as e:
+            raise SystemExit(f'--disc: {e}')
+        ck = load_checkpoint_file(ckpt, map_location='cpu')
+        hp = ck.get('hyper_parameters', {}) if isinstance(ck.get('hyper_parameters', {}), dict) else {}
+        self.hp = hp.get('args', hp)
+        self.global_step = int(ck.get('global_step', 0) or 0)
+        for net in nets:
+            net.train(stats == 'batch')
+        self.runners = tuple(D.DiscRunner(net, dtype) for net in nets)
+        self.gen = torch.Generator().manual_seed(int(seed))
+        self.frame_idx, self.rows = [], []
+
+    @torch.no_grad()
+    def add(self, x, x_recon):
+        """x, x_recon fp32 [B, 3, T, H, W] on the GPU: draws this batch's frames and appends its thirteen values (fp64 [13], device)"""
+        from .discriminator import gan_terms
+        fidx = torch.randint(0, x.shape[2], [x.shape[0]], generator=self.gen)
+        self.frame_idx.append(fidx)
+        x, x_recon = x.to(torch.float32).contiguous(), x_recon.to(torch.float32).contiguous()
+        vals = {}
+        for which in ('generator', 'discriminator'):
+            vals.update(gan_terms(self.hp, self.runners[0], self.runners[1], x, x_recon, fidx, self.global_step, which, update_running=False))
+        self.rows.append(torch.stack([vals[k] for k in DISC_COLUMNS]))
+        return self.rows[-1]
+
+    def result(self):
+        mean = torch.stack(self.rows).mean(0).cpu().tolist()
+        return dict(zip(DISC_COLUMNS, mean))
 
 
 def real_batches(args, device):
@@ -92,7 +143,7 @@ def real_batches(args, device):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    print(args)
+    print(args if args.disc else argparse.Namespace(**{k: v for k, v in vars(args).items() if not k.startswith('disc')}))
     from . import recon
     from .vqgan import load_vqgan
     device = torch.device('cuda')
@@ -118,6 +169,9 @@ def main(argv=None):
         from .fvd import frechet_distance, get_fvd_logits, polynomial_mmd
         from .measure_fvd import load_model
         i3d = load_model(args, device)
+    disc = DiscTerms(args.vqgan_ckpt, device, args.disc_dtype, args.disc_stats, args.seed) if args.disc else None
+    if disc is not None:
+        print(f'discriminators: compute dtype {args.disc_dtype}, {args.disc_stats} statistics, global_step {disc.global_step}')
     seed_everything(args.seed)
     acc = recon.ReconAccumulator(vqgan.n_codes, l1_weight=vqgan._hp("l1_weight", 4.0), device=device)
     saved, emb_real, emb_fake = [], [], []
@@ -127,6 +181,8 @@ def main(argv=None):
             x, u8 = x[:left].contiguous(), u8[:left].contiguous()
         st = vqgan.reconstruct_stats(x, clip_u8=u8, lpips_every=args.lpips_every if args.lpips else 0)
         acc.add(st)
+        if disc is not None:
+            disc.add(x, st["recon"])
         if args.save_np:
             saved.append(st["recon_u8"])
         if i3d is not None:
@@ -140,6 +196,9 @@ def main(argv=None):
         print(f'the split ended after {acc.n_clips} clips, fewer than --n_sample {args.n_sample}')
     row = acc.result()
     columns = list(recon.FIELDS) + (["LPIPS"] if args.lpips else [])
+    if disc is not None:
+        row.update(disc.result())
+        columns += DISC_COLUMNS
     if i3d is not None:
         real, fake = torch.cat(emb_real, 0), torch.cat(emb_fake, 0)
         row["rFVD"], row["rKVD"] = float(frechet_distance(fake, real)), float(polynomial_mmd(fake, real))
